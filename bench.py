@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """hoh-ANS MI355X bench: MB/s encode+decode (bit-exact) of synthetic 8-bit RGB.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, checks every step's status and that every slot
+decoded its input back (lossless), writes the last timed step's outputs when --dump-outputs DIR is
+given (dump_outputs: file sizes and seeded samples of the files and the decoded images as
+DIR/*.npy; the inputs are seeded, so equal arguments give equal arrays) and prints the result line.
+Everything else described below -- the SHA comparison with the reference's goldens, the
+one-in-flight and no-index measurements, the roofline, the live PMC passes, the detail legs, the
+single-stream leg, cpu_baseline and, at N > 1, the configs[3] leg -- runs only with --full.
 
 One step = one pass of the hot path over one batch of the workload, inputs resident in HBM:
   N = 1: choh -s0 of a batch of B = --batch (default 8) 8192x8192 images (BASELINE.json
@@ -31,8 +39,8 @@ issued in step order on one process group (hoh_ans.dist.run_pipeline).  A set-up
 step per slot (workspaces sized outside the timed region), then W warmup steps, then K timed.
 
 Outside the timed region: every slot's decoded image is compared with its input (lossless), and
-at N = 1 slot 0's file (seed 1) with the sha256 golden of the compiled reference (tests/golden).
-Also at N = 1: detail.single_image_MBps (one image at a time, host-synchronous calls) and
+with --full every slot's file with the sha256 golden of the compiled reference (tests/golden).
+Also with --full at N = 1: detail.single_image_MBps (one image at a time, host-synchronous calls) and
 detail.no_index_decode_MBps (dhoh of slot 0's file WITHOUT the side index: the serial rANS decode
 any foreign .hoh gets, checked lossless).
 
@@ -729,7 +737,8 @@ def shard_one_in_flight(ops, s, torch, hoh_ans, n=5):
     return iso, same
 
 
-def sharded_leg(args, W, H, D, B, K, warm, seed0, rank, world, dev, torch, hoh_ans, hd, one_in_flight=False):
+def sharded_leg(args, W, H, D, B, K, warm, seed0, rank, world, dev, torch, hoh_ans, hd, one_in_flight=False,
+                dump=None):
     """One N > 1 leg (or its one-rank rehearsal, --sharded): returns a dict of its numbers; on
     rank 0 the SHA of slot 0's first image's gathered file (seed seed0) is reported, and every slot's
     images' files of their last step against the reference choh's SHAs where known (each file is
@@ -738,6 +747,10 @@ def sharded_leg(args, W, H, D, B, K, warm, seed0, rank, world, dev, torch, hoh_a
     import torch.distributed as dist
     ops = GpuShardOps(args, W, H, seed0, rank, world, dev, torch, hoh_ans, hd, max(K, warm, D), B)
     slots, el, lossless = hd.run_sharded_leg(ops, D, K, warm)
+    if dump:      # this rank's blobs and decoded bands of the last timed step
+        last = slots[(K - 1) % D]
+        dump_outputs(dump, torch, last.out, ops.stride, [int(x) for x in ops.status[K - 1, 1:2 * B:2].tolist()],
+                     last.dec, ops.band, prefix="rank%d_" % rank if world > 1 else "")
     t_enc = sum(ev[0].elapsed_time(ev[1]) for s in slots for ev in s.events) * 1e-3
     t_dec = sum(ev[-2].elapsed_time(ev[-1]) for s in slots for ev in s.events) * 1e-3
     stats = {}
@@ -758,7 +771,7 @@ def sharded_leg(args, W, H, D, B, K, warm, seed0, rank, world, dev, torch, hoh_a
     # every slot's files of its last step (header + tile table + every rank's blob), hashed on the
     # rank that assembled each (image b of a slot on rank b % world), collected on every rank
     mine = {}
-    for s in slots:
+    for s in (slots if args.full else []):      # the SHA comparison with the reference's files: --full
         g = s.gather
         for b in g.own:
             mine[s.seeds[b]] = hashlib.sha256(g.files[g.row(b), :g.totals[b]].cpu().numpy().tobytes()).hexdigest()
@@ -796,6 +809,37 @@ def golden_bench_shas(W, H, noise):
                     if (r["spec"]["W"], r["spec"]["H"], r["spec"]["noise"], r["spec"]["speed"]) == (W, H, noise, 0)}
     except Exception:
         return {}
+
+
+DUMP_SEED = 0x686f68
+DUMP_FILE_SAMPLES, DUMP_IMAGE_SAMPLES = 1 << 22, 1 << 23    # float32 values over the B images: 16 + 32 MiB
+
+
+def dump_outputs(path, torch, out, stride, sizes, dec, img, prefix=""):
+    """--dump-outputs: what the last timed step handed its caller, as float arrays two builds can be
+    compared by: <prefix>file_sizes.npy (float64, the B files' or blobs' sizes),
+    <prefix>file_bytes_sample.npy (float32, B rows: each file's bytes at the positions floor(u * size)
+    of fixed seeded uniforms u -- the same positions whenever the sizes agree) and
+    <prefix>decoded_sample.npy (float32, B rows: each decoded image's bytes at fixed seeded
+    positions).  out holds file b at b * stride, dec image b at b * img.  The inputs are seeded too,
+    so the same arguments give the same arrays from run to run."""
+    import numpy as np
+    B = len(sizes)
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    u = rng.random(max(1, DUMP_FILE_SAMPLES // B))
+    pos = torch.from_numpy(rng.integers(0, img, min(img, max(1, DUMP_IMAGE_SAMPLES // B)))).to(dec.device)
+    files = np.zeros((B, u.size), np.float32)
+    images = np.zeros((B, pos.numel()), np.float32)
+    for b in range(B):
+        n = int(sizes[b])
+        if n > 0:
+            at = torch.from_numpy(np.minimum((u * n).astype(np.int64), n - 1)).to(out.device)
+            files[b] = out[b * stride:b * stride + n][at].float().cpu().numpy()
+        images[b] = dec[b * img:(b + 1) * img][pos].float().cpu().numpy()
+    np.save(os.path.join(path, prefix + "file_sizes.npy"), np.asarray(sizes, np.float64))
+    np.save(os.path.join(path, prefix + "file_bytes_sample.npy"), files)
+    np.save(os.path.join(path, prefix + "decoded_sample.npy"), images)
 
 
 STRONG_SIDE, STRONG_SEED = 16384, 2     # configs[3]; seed 2 is the reference choh's golden file
@@ -863,7 +907,17 @@ def main():
     ap.add_argument("--pmc-probe-speed", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--pmc-speed", type=int, default=4,
                     help="the -sN encode whose kernels get live PMC roofline fractions (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the one-in-flight and no-index measurements, the roofline, the "
+                         "live PMC passes, the detail legs, the single-stream leg, the CPU baseline, the configs[3] "
+                         "leg (N > 1 / --sharded) and the SHA comparison of every file with the reference's goldens "
+                         "(each still switched off by its own --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (file sizes, seeded "
+                         "samples of the files' bytes and of the decoded images) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:      # a plain run: set up, warm up, time the steps, dump, print
+        args.no_pmc = args.no_legs = args.no_config2 = args.no_cpu_baseline = args.no_strong_leg = True
     if args.size <= 0:
         args.size = STRONG_SIDE if args.strong else 8192
     if args.pmc_probe:
@@ -981,7 +1035,8 @@ def sharded_main(args, D, B, world, rank, dev, torch, hoh_ans, hd):
     K, warm = args.steps, args.warmup
     seed0 = STRONG_SEED if (args.strong and W == STRONG_SIDE) else args.seed
     Bp = strong_batch(W, H, world, B) if args.strong else B
-    p = sharded_leg(args, W, H, D, Bp, K, warm, seed0, rank, world, dev, torch, hoh_ans, hd, one_in_flight=True)
+    p = sharded_leg(args, W, H, D, Bp, K, warm, seed0, rank, world, dev, torch, hoh_ans, hd, one_in_flight=args.full,
+                    dump=args.dump_outputs)
     strong = None
     if not args.strong and not args.no_strong_leg and STRONG_SIDE // 256 >= world:
         Ds = max(1, min(args.strong_inflight, D))
@@ -1019,7 +1074,7 @@ def sharded_main(args, D, B, world, rank, dev, torch, hoh_ans, hd):
             "ratio": round(ratio, 5),
             "lossless": p["lossless"],
             "file_sha256": p["sha"],
-            "bit_exact_vs_reference": (p["sha"] == gw) if gw else None,
+            "bit_exact_vs_reference": (p["sha"] == gw) if (gw and p["sha"]) else None,      # hashed with --full
             "slot_files_bit_exact": "%d of %d" % (sum(checked.values()), len(checked)),
             "slot_files_checked_seeds": sorted(checked),
             "one_in_flight_shard_bytes_equal_batched": p["iso_same_bytes"],
@@ -1138,10 +1193,14 @@ def batch_main(args, D, B, dev, torch, hoh_ans, hd):
     torch.cuda.synchronize()
     el = time.perf_counter() - t
     st = check_status(K)
+    if args.dump_outputs:
+        last = slots[(K - 1) % D]
+        dump_outputs(args.dump_outputs, torch, last.out, stride, [int(st[K - 1, 2 * b + 1]) for b in range(B)],
+                     last.dec, img)
     bad_dec = [(k, b) for k, s in enumerate(slots) for b in range(B)
                if not bool(torch.equal(s.dec[b * img:(b + 1) * img], s.rgb[b * img:(b + 1) * img]))]
     lossless = not bad_dec
-    gb = golden_bench_shas(W, H, args.noise)
+    gb = golden_bench_shas(W, H, args.noise) if args.full else {}      # the SHA comparison: --full
     match, checked, nogold, comp, bad_sha = 0, 0, [], None, []
     for k, s in enumerate(slots):
         if k >= K:
@@ -1160,6 +1219,8 @@ def batch_main(args, D, B, dev, torch, hoh_ans, hd):
             match += ok
             if not ok:
                 bad_sha.append((k, b, sd, n_b))
+    if not args.full:
+        nogold = []      # nothing was compared
     if bad_dec or bad_sha:
         print("batch_main: lossless failures (slot, image) %s; SHA mismatches (slot, image, seed, size) %s"
               % (bad_dec, bad_sha), file=sys.stderr)
@@ -1272,6 +1333,11 @@ def single_main(args, D, dev, torch, hoh_ans, hd, pmc, pmc_note, pmc_speed):
     torch.cuda.synchronize()
     el = time.perf_counter() - t
     check_status(K)
+    st = status[:K].cpu().numpy()
+    if args.dump_outputs:      # the last timed step's files and decoded images, before anything reuses the slots
+        last = slots[(K - 1) % D]
+        dump_outputs(args.dump_outputs, torch, last.out, stride, [int(st[K - 1, 2 * b + 1]) for b in range(B)],
+                     last.dec, img)
     stats = {}
     for s in slots:
         for k, (tot, cnt) in s.ctx.kernel_stats().items():
@@ -1283,9 +1349,60 @@ def single_main(args, D, dev, torch, hoh_ans, hd, pmc, pmc_note, pmc_speed):
         for ev in s.events:
             t_enc += ev[0].elapsed_time(ev[1]) * 1e-3
             t_dec += ev[-2].elapsed_time(ev[-1]) * 1e-3
+    # every slot lossless: the one check a plain run makes beside the steps' statuses
+    lossless = all(bool(torch.equal(s.dec, s.rgb)) for s in slots)
+    raw_total = W * H * 3
+    value = raw_total * B * K / el / 1e6
+    kavg = {k: v[0] / v[1] for k, v in stats.items() if v[1]}
+    comp_total = int(st[((K - 1) // D) * D, 1])      # slot 0's first image (seed --seed), its last timed step
+    ratio = comp_total / raw_total
+    res = {
+        "metric": metric_name(),
+        "value": round(value, 2),
+        "unit": "MB/s",
+        "n_gpus": 1,
+        "steps": K,
+        "warmup": warm,
+        "ms_per_step": round(el / K * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": ("%dx%d synthetic RGB (gradient + triangular noise k=%d, seeds %d..%d: one image each), "
+                         "256x256 tiles, choh -s0 encode + dhoh decode, %s, %d slot(s) x %d image(s) per step "
+                         "(%s) = %d images in flight per GPU, %s hardware queues"
+                         % (W, H, args.noise, args.seed, args.seed + D * B - 1,
+                            "side index" if not args.no_index else "serial decode", D, B,
+                            "batched calls hoh_encode_images_async / hoh_decode_images_async" if B > 1 else
+                            "hoh_encode_image_async / hoh_decode_image_async", D * B, hw_queue_note())),
+            "W": W, "H": H, "tiles": (W // 256) * (H // 256), "per_gpu": "%dx%d" % (W, rows), "batch": B,
+            "parallelism": "1 GPU",
+        },
+        "detail": {
+            "inflight": D * B,
+            "slots": D,
+            "batch": B,
+            "hw_queues": hw_queue_note(),
+            "warmup_requested": args.warmup,
+            "latency_ms_enc": round(t_enc / K * 1e3, 3),
+            "latency_ms_dec": round(t_dec / K * 1e3, 3),
+            "compressed_bytes": comp_total,
+            "ratio": round(ratio, 5),
+            "lossless": lossless,
+            "setup_steps": D,
+            "kernel_avg_ms_under_load": {k: round(v, 4) for k, v in kavg.items()},
+        },
+    }
+    if not args.full:      # a plain run ends here
+        print(json.dumps(res), flush=True)
+        if not lossless:
+            sys.exit(3)
+        return
 
-    # per-kernel durations and the per-image rate with ONE image in flight (host-synchronous
-    # calls), and the no-index (serial rANS) decode of slot 0's file
+    # --full.  Per-kernel durations and the per-image rate with ONE image in flight
+    # (host-synchronous calls), and the no-index (serial rANS) decode of slot 0's file
     s0 = slots[0]
     noix_ms, noix_ok = None, None
     with torch.cuda.stream(s0.stream):
@@ -1315,13 +1432,12 @@ def single_main(args, D, dev, torch, hoh_ans, hd, pmc, pmc_note, pmc_speed):
             noix_ok = bool(torch.equal(noix, s0.rgb0))
             del noix
 
-    # checks outside the timed region: every slot lossless, and EVERY slot's file (its last
-    # timed step's) against the reference choh's sha256 for that slot's seed
-    # (tests/golden/golden_bench.json, made by tests/golden/make_golden_bench.py)
-    lossless = all(bool(torch.equal(s.dec, s.rgb)) for s in slots)
+    # checks outside the timed region: every slot lossless (again, after the one-in-flight calls),
+    # and EVERY slot's file (its last timed step's) against the reference choh's sha256 for that
+    # slot's seed (tests/golden/golden_bench.json, made by tests/golden/make_golden_bench.py)
+    lossless = lossless and all(bool(torch.equal(s.dec, s.rgb)) for s in slots)
     sha = hashlib.sha256(s0.out0[:n0].cpu().numpy().tobytes()).hexdigest()
     gb = golden_bench_shas(W, H, args.noise)
-    st = status[:K].cpu().numpy()
     slot_match, slot_checked, slot_nogolden = 0, 0, []
     for k, s in enumerate(slots):
         if k >= K:
@@ -1336,71 +1452,29 @@ def single_main(args, D, dev, torch, hoh_ans, hd, pmc, pmc_note, pmc_speed):
                 continue
             slot_checked += 1
             slot_match += hashlib.sha256(s.out[b * stride:b * stride + n_k].cpu().numpy().tobytes()).hexdigest() == want
-    comp_total = n0
-    raw_total = W * H * 3
-    value = raw_total * B * K / el / 1e6
     legs = {}
     if not args.no_legs:      # after the checks: the legs reuse the slots' buffers
         legs = extra_legs(args, slots, W, H, D, B, stride, status, torch, hoh_ans, hd)
 
-    kavg = {k: v[0] / v[1] for k, v in stats.items() if v[1]}
-    ratio = comp_total / raw_total
-    roof = roofline_obj(iso.get(DOM) or None, kavg, ratio, W * rows * 3, raw_total, K, el, pmc, B)
     golden = golden_sha(W, H, args.seed, args.noise)
-    res = {
-        "metric": metric_name(),
-        "value": round(value, 2),
-        "unit": "MB/s",
-        "n_gpus": 1,
-        "steps": K,
-        "warmup": warm,
-        "ms_per_step": round(el / K * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {
-            "workload": ("%dx%d synthetic RGB (gradient + triangular noise k=%d, seeds %d..%d: one image each), "
-                         "256x256 tiles, choh -s0 encode + dhoh decode, %s, %d slot(s) x %d image(s) per step "
-                         "(%s) = %d images in flight per GPU, %s hardware queues"
-                         % (W, H, args.noise, args.seed, args.seed + D * B - 1,
-                            "side index" if not args.no_index else "serial decode", D, B,
-                            "batched calls hoh_encode_images_async / hoh_decode_images_async" if B > 1 else
-                            "hoh_encode_image_async / hoh_decode_image_async", D * B, hw_queue_note())),
-            "W": W, "H": H, "tiles": (W // 256) * (H // 256), "per_gpu": "%dx%d" % (W, rows), "batch": B,
-            "parallelism": "1 GPU",
-        },
-        "roofline": roof,
-        "detail": {
-            "inflight": D * B,
-            "slots": D,
-            "batch": B,
-            "hw_queues": hw_queue_note(),
-            "warmup_requested": args.warmup,
-            "latency_ms_enc": round(t_enc / K * 1e3, 3),
-            "latency_ms_dec": round(t_dec / K * 1e3, 3),
-            "compressed_bytes": comp_total,
-            "ratio": round(ratio, 5),
-            "lossless": lossless,
-            "file_sha256": sha,
-            "bit_exact_vs_reference": (sha == golden) if golden else None,
-            "slot_files_bit_exact": "%d of %d" % (slot_match, slot_checked),
-            "slot_files_bit_exact_all": (slot_match == slot_checked and not slot_nogolden) if slot_checked else None,
-            "slot_files_no_golden_seeds": slot_nogolden,
-            "single_image_MBps": round(raw_total / single_ms / 1e3, 1) if single_ms else None,
-            "single_image_ms": round(single_ms, 3) if single_ms else None,
-            "no_index_decode_MBps": round(raw_total / noix_ms / 1e3, 1) if noix_ms else None,
-            "no_index_decode_lossless": noix_ok,
-            "setup_steps": D,
-            **legs,
-            "kernel_avg_ms_under_load": {k: round(v, 4) for k, v in kavg.items()},
-            "kernel_avg_ms_one_in_flight": {k: round(v, 4) for k, v in iso.items()},
-            "pmc_hbm_bytes_per_launch": pmc,
-            "pmc_source": pmc_note,
-            "speed_roofline_s%d" % args.pmc_speed: pmc_speed,
-        },
-    }
+    res["roofline"] = roofline_obj(iso.get(DOM) or None, kavg, ratio, W * rows * 3, raw_total, K, el, pmc, B)
+    res["detail"].update({
+        "lossless": lossless,
+        "file_sha256": sha,
+        "bit_exact_vs_reference": (sha == golden) if golden else None,
+        "slot_files_bit_exact": "%d of %d" % (slot_match, slot_checked),
+        "slot_files_bit_exact_all": (slot_match == slot_checked and not slot_nogolden) if slot_checked else None,
+        "slot_files_no_golden_seeds": slot_nogolden,
+        "single_image_MBps": round(raw_total / single_ms / 1e3, 1) if single_ms else None,
+        "single_image_ms": round(single_ms, 3) if single_ms else None,
+        "no_index_decode_MBps": round(raw_total / noix_ms / 1e3, 1) if noix_ms else None,
+        "no_index_decode_lossless": noix_ok,
+        **legs,
+        "kernel_avg_ms_one_in_flight": {k: round(v, 4) for k, v in iso.items()},
+        "pmc_hbm_bytes_per_launch": pmc,
+        "pmc_source": pmc_note,
+        "speed_roofline_s%d" % args.pmc_speed: pmc_speed,
+    })
     if not args.no_config2:
         try:
             res["detail"]["config2_single_stream"] = config2_leg(args)

@@ -4,7 +4,7 @@
 #   MODE q4:   --hw-queues 4 (HIP's default) without legs/baselines
 #   MODE legs: legs only (no cpu baseline / config2 / pmc)
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/../.."; ROOT=$PWD; mkdir -p bench_out; export TMPDIR=/tmp
 tag=$1; mode=${2:-full}
 case $mode in
   full) args="--steps 20 --warmup 5" ;;
@@ -12,7 +12,7 @@ case $mode in
   legs) args="--steps 20 --warmup 5 --no-cpu-baseline --no-config2 --no-pmc" ;;
   *)    args="$mode" ;;
 esac
-timeout -k 10 900 python -u bench.py $args > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+timeout -k 10 900 python -u bench.py --full $args > bench_out/${tag}_bench.json 2> bench_out/${tag}_bench.err
 rc=$?
-tail -c 3000 gpurun_out/${tag}_bench.json; tail -3 gpurun_out/${tag}_bench.err
+tail -c 3000 bench_out/${tag}_bench.json; tail -3 bench_out/${tag}_bench.err
 exit $rc

@@ -3,13 +3,13 @@
 # default queues) under rocprofv3 --kernel-trace --stats; per-kernel totals per image.
 # Usage: bash tools/scripts/r5_pipeprof.sh TAG [STEPS]
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/../.."; ROOT=$PWD; mkdir -p bench_out; export TMPDIR=/tmp
 tag=$1; steps=${2:-30}
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${tag} -o p -- \
-  python3 bench.py --batch-only --steps $steps --warmup 4 --no-cpu-baseline --no-pmc > gpurun_out/${tag}.log 2>&1 \
-  || { tail -20 gpurun_out/${tag}.log; exit 1; }
-grep '^{' gpurun_out/${tag}.log | tail -1 | cut -c1-400
-python3 - gpurun_out/${tag} <<'PY'
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d bench_out/${tag} -o p -- \
+  python3 bench.py --full --batch-only --steps $steps --warmup 4 --no-cpu-baseline --no-pmc > bench_out/${tag}.log 2>&1 \
+  || { tail -20 bench_out/${tag}.log; exit 1; }
+grep '^{' bench_out/${tag}.log | tail -1 | cut -c1-400
+python3 - bench_out/${tag} <<'PY'
 import glob, sqlite3, sys
 db = sqlite3.connect(glob.glob(sys.argv[1] + "/*.db")[0])
 rows = db.execute("select name, count(*), sum(end-start)/1e6 from kernels group by name order by 3 desc").fetchall()

@@ -17,8 +17,8 @@
 #           $PMC_PROG replaces the probe (e.g. "tools/scripts/natural_prof.py 8192 0 1")
 # usage: round_check.sh OUTDIR stage...
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
-O=gpurun_out/$1; shift; mkdir -p $O
+cd "$(dirname "$0")/../.."; ROOT=$PWD; export TMPDIR=/tmp
+O=bench_out/$1; shift; mkdir -p $O
 for st in "$@"; do
   case $st in
     tests)
@@ -26,8 +26,8 @@ for st in "$@"; do
         || { tail -30 $O/gputests.log; exit 1; }
       tail -2 $O/gputests.log ;;
     bench)
-      timeout -k 10 240 python -u bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
-      timeout -k 10 240 python -u bench.py --sharded --steps 20 --warmup 5 > $O/sharded.json 2> $O/sharded.err \
+      timeout -k 10 240 python -u bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+      timeout -k 10 240 python -u bench.py --full --sharded --steps 20 --warmup 5 > $O/sharded.json 2> $O/sharded.err \
         || { tail $O/sharded.err; exit 1; }
       python3 - $O <<'PY'
 import json, sys
@@ -42,8 +42,8 @@ PY
       B="--no-legs --no-pmc --no-cpu-baseline --no-config2"
       for v in base $VARS; do
         n=$(basename $v .so)
-        if [ "$v" = base ]; then unset HOH_LIB; else export HOH_LIB=$GRAFT_REPO_ROOT/$v; fi
-        timeout -k 10 200 python -u bench.py --steps 100 --warmup 5 $B > $O/ab_${n}.json 2> $O/ab_err || { tail $O/ab_err; exit 1; }
+        if [ "$v" = base ]; then unset HOH_LIB; else export HOH_LIB=$ROOT/$v; fi
+        timeout -k 10 200 python -u bench.py --full --steps 100 --warmup 5 $B > $O/ab_${n}.json 2> $O/ab_err || { tail $O/ab_err; exit 1; }
         python3 -c "import json; d=json.loads(open('$O/ab_${n}.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$n', d['value'], r['avg_launch_ms'], r['avg_launch_ms_under_load'], d['detail']['bit_exact_vs_reference'], d['detail']['slot_files_bit_exact'])"
       done
       unset HOH_LIB ;;
@@ -53,14 +53,14 @@ PY
       for ev in ${AB_ENVS:--}; do
         E=""; [ "$ev" != "-" ] && E=$(echo $ev | tr ',' ' ')
         n=$(echo $ev | tr ',=' '__')
-        timeout -k 10 200 env $E python -u bench.py --steps 100 --warmup 5 $B > $O/abe_${n}.json 2> $O/ab_err || { tail $O/ab_err; exit 1; }
+        timeout -k 10 200 env $E python -u bench.py --full --steps 100 --warmup 5 $B > $O/abe_${n}.json 2> $O/ab_err || { tail $O/ab_err; exit 1; }
         python3 -c "import json; d=json.loads(open('$O/abe_${n}.json').read().strip().splitlines()[-1]); r=d['roofline']; print('[$ev]', d['value'], r['avg_launch_ms'], r['avg_launch_ms_under_load'], d['detail']['bit_exact_vs_reference'], d['detail']['slot_files_bit_exact'])"
       done ;;
     inflight)
       B="--no-legs --no-pmc --no-cpu-baseline --no-config2"
       for dq in ${INFLIGHT:-16:0 20:0 24:0 28:0 32:0 40:0 24:24 28:28}; do
         d=${dq%:*}; q=${dq#*:}
-        timeout -k 10 200 python -u bench.py --steps 100 --warmup 5 --inflight $d --hw-queues $q $B > $O/if_${d}_${q}.json 2> $O/if_err \
+        timeout -k 10 200 python -u bench.py --full --steps 100 --warmup 5 --inflight $d --hw-queues $q $B > $O/if_${d}_${q}.json 2> $O/if_err \
           || { tail $O/if_err; exit 1; }
         python3 -c "import json; d=json.load(open('$O/if_${d}_${q}.json')); print('inflight $d queues $q', d['value'], d['detail']['latency_ms_enc'], d['detail']['latency_ms_dec'])"
       done ;;
@@ -71,7 +71,7 @@ PY
           timeout -k 10 120 env $E python3 tools/scripts/noix_bench.py $kind 8192 5 > $O/noix.txt 2>&1 || { tail $O/noix.txt; exit 1; }
           echo "[$ev] $(grep no-index $O/noix.txt | cut -c1-160)"
         done
-        timeout -k 10 200 env $E python -u bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-config2 > $O/noixb.json 2> $O/noixb.err \
+        timeout -k 10 200 env $E python -u bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-config2 > $O/noixb.json 2> $O/noixb.err \
           || { tail $O/noixb.err; exit 1; }
         python3 -c "import json; d=json.loads(open('$O/noixb.json').read().strip().splitlines()[-1])['detail']; print('[$ev] pipeline', d.get('no_index_pipeline_MBps'), d.get('no_index_pipeline_lossless'), 'single', d.get('no_index_decode_MBps'))"
       done ;;
@@ -84,8 +84,8 @@ PY
         done
       done ;;
     trace)
-      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/trace -o run \
-        -- python3 $GRAFT_REPO_ROOT/bench.py --steps 40 --warmup 5 --no-legs --no-pmc --no-cpu-baseline --no-config2) \
+      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $ROOT/$O/trace -o run \
+        -- python3 $ROOT/bench.py --full --steps 40 --warmup 5 --no-legs --no-pmc --no-cpu-baseline --no-config2) \
         > $O/trace.log 2>&1 || { tail $O/trace.log; exit 1; }
       ls -la $(find $O/trace -name "*kernel_trace.csv") ;;
     pmc)
@@ -94,14 +94,14 @@ PY
       IFS=';' read -ra SA <<< "$SETS"
       for set in "${SA[@]}"; do
         k=$((k+1))
-        (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc $set --output-format csv -d $GRAFT_REPO_ROOT/$O/pmc$k -o p \
-          -- python3 $GRAFT_REPO_ROOT/${PMC_PROG:-bench.py --pmc-probe}) > $O/pmc$k.log 2>&1 || { tail -5 $O/pmc$k.log; exit 1; }
+        (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc $set --output-format csv -d $ROOT/$O/pmc$k -o p \
+          -- python3 $ROOT/${PMC_PROG:-bench.py --pmc-probe}) > $O/pmc$k.log 2>&1 || { tail -5 $O/pmc$k.log; exit 1; }
       done
       python3 tools/scripts/pmc_summary2.py $O/pmc* > $O/pmc_summary.txt; cat $O/pmc_summary.txt ;;
     nat)
       for sp in ${NAT_PROF_SPEEDS:-1 2 3 4}; do
-        (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/nat$sp -o run \
-          -- python3 $GRAFT_REPO_ROOT/tools/scripts/natural_prof.py 8192 $sp 2) > $O/nat$sp.txt 2>&1 || { tail $O/nat$sp.txt; exit 1; }
+        (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/nat$sp -o run \
+          -- python3 $ROOT/tools/scripts/natural_prof.py 8192 $sp 2) > $O/nat$sp.txt 2>&1 || { tail $O/nat$sp.txt; exit 1; }
         grep "^natural" $O/nat$sp.txt
         python3 tools/scripts/kstats.py $O/nat$sp 6 2>/dev/null || head -7 $O/nat$sp/run_kernel_stats.csv | cut -d, -f1-4
       done ;;
