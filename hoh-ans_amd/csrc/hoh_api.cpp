@@ -77,6 +77,7 @@ struct hoh_ctx {
   uint64_t* pinned = nullptr;   // small host staging (status words, sizes)
   int profiling = 0;
   int noix = HOH_NOIX_ADAPTIVE;  // HOH_OPT_NOIX_DECODER
+  int decodable = 0;            // HOH_OPT_DECODABLE
   std::vector<std::string> knames;      // names of the marks recorded by the current call
   std::vector<hipEvent_t> kev;          // event pool, kev[0..nmark) recorded by the current call
   size_t nmark = 0;
@@ -211,6 +212,10 @@ int hoh_ctx_set_option(hoh_ctx* c, int option, int64_t value) {
     case HOH_OPT_NOIX_DECODER:
       if (value < HOH_NOIX_ADAPTIVE || value > HOH_NOIX_WAVE) return HOH_E_ARG;
       c->noix = (int)value;
+      return HOH_OK;
+    case HOH_OPT_DECODABLE:
+      if (value != 0 && value != 1) return HOH_E_ARG;
+      c->decodable = (int)value;
       return HOH_OK;
   }
   return HOH_E_ARG;
@@ -388,6 +393,7 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
   EncodeJob j{};
   memset(&j, 0, sizeof(j));
   j.speed = speed;
+  j.decodable = c->decodable;
   j.spt = speed ? SPT_S : SK_PER_TILE;
   j.rgb = d_rgb; j.W = W; j.H = H;
   j.xt = xt; j.yt = yt; j.tw = tw; j.th = th;
@@ -842,6 +848,7 @@ int encode_streams_impl(hoh_ctx* c, const uint16_t* d_syms, const uint64_t* off,
   j.out = d_out;
   j.cap = ~0ull;
   j.spt = 1;
+  j.decodable = c->decodable;                 // k_tables: no lossy raw table (Q4)
   if (hipMemcpyAsync(c->streams.p, st.data(), st.size() * sizeof(StreamInfo), hipMemcpyHostToDevice, s) != hipSuccess) return HOH_E_HIP;
   if (hipMemsetAsync(c->misc.p, 0, 64, s) != hipSuccess) return HOH_E_HIP;
   launch_tables(j, nstreams, s);
@@ -981,4 +988,5 @@ uint64_t* ctx_pinned(hoh_ctx* c) { return c->pinned; }
 int ctx_device(hoh_ctx* c) { return c->device; }
 int ctx_cus(hoh_ctx* c) { return c->cus; }
 int ctx_noix(hoh_ctx* c) { return c->noix; }
+int ctx_decodable(hoh_ctx* c) { return c->decodable; }
 void ctx_mark(hoh_ctx* c, hipStream_t s, const char* name, bool reset) { prof_mark(c, s, name, reset); }

@@ -30,7 +30,25 @@ struct DecTile {
   int32_t x0, y0, w, h;
   uint64_t off;           // byte offset of the tile in the file
   uint32_t mode, nmatch;
-  uint32_t err, pad;
+  uint32_t err, gen;      // gen: 1 = a general tile (GenTile), decoded by k_dgen
+};
+
+// General tiles: anything beyond the -s0 shape (mode 128, three LZ streams, 1x1 0x0010 layers) --
+// RGB mode 2, a fourth LZ stream (16-bit distances), layers with a predictor map.  Their extra
+// streams (the fourth LZ stream and the three map streams) take the stream slots
+// [ntiles * SK_PER_TILE + 4 t, + 4), behind the numbering the side index matches on.
+#define HOH_GEN_MAPCAP 4096   // predictor-map cells per layer the decoder takes (a 4-px grid on a 256^2 tile)
+#define HOH_GEN_XS 4          // extra stream slots per tile: the fourth LZ stream, then the three maps
+struct GenLayer {
+  uint32_t xt, yt;        // predictor grid
+  uint32_t nmask;         // masks listed in the layer header (1..16)
+  uint32_t mapped;        // 1: a map stream of xt * yt indices into masks; 0: masks[0] everywhere
+  uint16_t masks[16];
+};
+struct GenTile {
+  uint32_t nlz;           // LZ streams (3 or 4)
+  uint32_t pad;
+  GenLayer L[3];
 };
 
 struct DecWork {
@@ -57,6 +75,7 @@ uint64_t* ctx_pinned(hoh_ctx* c);
 int ctx_device(hoh_ctx* c);
 int ctx_cus(hoh_ctx* c);
 int ctx_noix(hoh_ctx* c);                  // HOH_OPT_NOIX_DECODER (include/hoh_ans.h)
+int ctx_decodable(hoh_ctx* c);             // HOH_OPT_DECODABLE
 void ctx_mark(hoh_ctx* c, hipStream_t s, const char* name, bool reset);
 
 // Per-context device scratch for the host-buffer entry points (encode_entropy, decode_entropy,

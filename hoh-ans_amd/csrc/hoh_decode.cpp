@@ -144,7 +144,7 @@ int hoh_entropy_parse(const uint8_t* in, size_t in_size, size_t bp, hoh_entropy_
   if (p >= in_size) return HOH_E_CORRUPT;
   const uint8_t meta = in[p++];
   h->entropy_mode = meta >> 7;
-  h->prob_bits = (meta & 0x3c) >> 2;
+  h->prob_bits = (meta & 0x7c) >> 2;                                  // 16..19 carry into bit 6 (k_decode.hip, parse_stream)
   h->table_mode = meta & 3;
   if (!h->entropy_mode) {                                              // stored (:278-290)
     h->table_end = p;

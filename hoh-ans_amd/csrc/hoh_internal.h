@@ -185,6 +185,7 @@ struct EncodeJob {
   uint32_t npix_cap;      // max pixels of one tile (per-plane stride of the residual arena)
   uint32_t lz_cap;        // symbols per LZ stream slot
   int speed;              // cruncher_mode (-sN)
+  int decodable;          // HOH_OPT_DECODABLE: every layer carries the whole stream its header describes
   int spt;                // streams per tile: SK_PER_TILE (-s0) or SPT_S
   // arenas
   uint16_t* sym;          // residual planes + LZ symbols

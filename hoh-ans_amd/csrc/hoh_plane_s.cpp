@@ -137,6 +137,21 @@ int layer_encode_search(hoh_ctx* c, const uint16_t* data, size_t n, int w, int h
   if ((r = encode_one(c, dcl.as<uint16_t>(), nc, range, 16, t1, s))) return r;
   if ((r = encode_one(c, dcl.as<uint16_t>(), nc, range, 15, t2, s))) return r;
   const bool up = t1.size() < t2.size();
+  if (ctx_decodable(c)) {
+    // HOH_OPT_DECODABLE: one whole stream of the residuals the header describes, the first
+    // candidate of strictly smallest size among 16, 17, 18, 19 or 15, 14, 13, 12 (no MED stream,
+    // no depth bound, nothing stale)
+    std::vector<uint8_t>& best = up ? t1 : t2;
+    for (int k = 0; k < 3; k++) {
+      if ((r = encode_one(c, dcl.as<uint16_t>(), nc, range, up ? 17 + k : 14 - k, tmp, s))) return r;
+      if (tmp.size() < best.size()) best.swap(tmp);
+    }
+    *written = hdr.size() + best.size();
+    if (*written > cap) return HOH_E_CAP;
+    memcpy(out, hdr.data(), hdr.size());
+    memcpy(out + hdr.size(), best.data(), best.size());
+    return HOH_OK;
+  }
   const size_t t12 = up ? t1.size() : t2.size();
   if (t12 < possible) possible = t12;                                 // not swapped (Q14)
   for (int k = 0; k < 3; k++) {

@@ -14,6 +14,7 @@
 //             subtract-green, one wave per tile, anti-diagonal wavefront over 64-row bands.
 //  k_dunpred_lz: tiles with LZ copies, serial raster walk.
 #include "hoh_dec.h"
+#include "hoh_pred.h"
 #include "../../include/hoh_ans.h"
 #include <string.h>
 #include <stdlib.h>
@@ -62,7 +63,17 @@ struct DecJob {
   int nimg, img_tiles;          // batch (hoh_decode_images_async): nimg files of img_tiles tiles, the
   uint64_t in_stride;           //   image their stack, file i at in + i * in_stride (nimg <= 1: one file)
   uint32_t exp;                 // measurement what-ifs (knob EXP, knob builds only; 0 in the product)
+  GenTile* gen;                 // [tile] general tiles' layer headers (DecTile.gen, k_dgen)
 };
+
+// general tiles' extra streams: slot k (0: the fourth LZ stream, 1..3: the layers' maps) of tile t,
+// and where their symbols go in dsym (behind the planes and the three LZ streams of every tile)
+__host__ __device__ inline int gen_sid(const DecJob& j, int t, int k) { return j.ntiles * SK_PER_TILE + t * HOH_GEN_XS + k; }
+__host__ __device__ inline size_t gen_sym_per_tile(const DecJob& j) { return (size_t)j.lz_cap + 3 * (size_t)HOH_GEN_MAPCAP; }
+__host__ __device__ inline size_t gen_sym_off(const DecJob& j, int t, int k) {
+  return (size_t)j.ntiles * 3 * ((size_t)j.plane_cap + j.lz_cap) + (size_t)t * gen_sym_per_tile(j) +
+         (k ? (size_t)j.lz_cap + (size_t)(k - 1) * HOH_GEN_MAPCAP : 0);
+}
 
 __device__ __forceinline__ uint64_t rd_varint(const uint8_t* b, uint64_t& p) {
   uint64_t b0 = b[p++];
@@ -148,7 +159,7 @@ __global__ __launch_bounds__(1024) void k_dtable(DecJob j) {
     t.x0 = xo; t.y0 = yo;
     t.w = min(j.tw, j.W - xo); t.h = min(j.th, j.H - yo);
     t.off = i == 0 ? 0 : (j.tsizes ? j.tsizes[ib + i - 1] : 0);
-    t.mode = 0; t.nmatch = 0; t.err = 0; t.pad = 0;
+    t.mode = 0; t.nmatch = 0; t.err = 0; t.gen = 0;
     tiles[i] = t;
   }
   if (tid == 0) { tend = fb + j.prefix; serial = 0; }
@@ -234,7 +245,11 @@ __device__ bool parse_stream(const DecJob& j, uint64_t& p, int sid, uint64_t out
     return true;
   }
   d.mode = SM_RANS;
-  d.pb = (meta & 0x3c) >> 2;
+  // entropy_encoding.hpp:138 writes (mode << 7) + (prob_bits << 2) + table mode: prob_bits 16..19
+  // (the upper ladder of layer_encode.hpp:334-362) carry into bit 6, which the reference's reader
+  // masks off (entropy_decoding.hpp:153 -- it cannot read such a stream); five bits read them all
+  d.pb = (meta & 0x7c) >> 2;
+  if (d.pb > 19) return false;
   d.tsm = meta & 3;
   if (d.pb == 0 || (1u << d.pb) < range) return false;
   d.table_off = p;
@@ -348,40 +363,79 @@ __global__ __launch_bounds__(64) void k_dparse(DecJob job) {
   if (ok) {
     p += 2;
     ti.mode = j.in[p++];
-    if (ti.mode != 128) { ok = false; err = 2; }          // grey / bitimage / palette / rgb
+    if (ti.mode != 128 && ti.mode != 2) { ok = false; err = 2; }   // grey / bitimage / palette
   }
+  // Tiles of the -s0 shape (mode 128, three LZ streams, three 1x1 0x0010 layers) keep their
+  // kernels; anything else the format defines here (RGB mode 2, the fourth LZ stream of
+  // un_lz.hpp:138-165, predictor-map layers of layer_decode.hpp:196-256) makes a general tile
+  GenTile g;
+  memset(&g, 0, sizeof(g));
+  g.nlz = 3;
+  bool general = ok && ti.mode == 2;
+  const uint32_t npix = (uint32_t)ti.w * (uint32_t)ti.h;
   if (ok) {
     const uint8_t lzt = j.in[p++];
     const size_t lzbase = (size_t)j.ntiles * 3 * j.plane_cap + (size_t)t * 3 * j.lz_cap;
     if (lzt != 0x03) { ok = false; err = 2; }
-    for (int k = 0; k < 3 && ok; k++) ok = parse_stream(j, p, t * SK_PER_TILE + k, lzbase + (size_t)k * j.lz_cap, lane);
-    if (ok && p + 1 < j.size && j.in[p] == 0x81 && j.in[p + 1] == 0x7f) { ok = false; err = 2; }  // 4th LZ stream (-s>=1)
+    for (int k = 0; k < 3 && ok; k++) {
+      ok = parse_stream(j, p, t * SK_PER_TILE + k, lzbase + (size_t)k * j.lz_cap, lane);
+      if (ok && j.streams[t * SK_PER_TILE + k].n > j.lz_cap) ok = false;
+    }
+    if (ok && p < j.size && j.in[p] != 0x24) {                  // a fourth stream: the distances' high bytes
+      ok = parse_stream(j, p, gen_sid(j, t, 0), gen_sym_off(j, t, 0), lane);
+      if (ok && j.streams[gen_sid(j, t, 0)].n > j.lz_cap) ok = false;
+      g.nlz = 4;
+      general = true;
+    }
   }
   if (ok) {
-    if (j.in[p] != 0x24) ok = false;
+    if (p >= j.size || j.in[p] != 0x24) ok = false;
     p++;
   }
+  if (ok && p + 6 > j.size) ok = false;
   if (ok) {
     const uint64_t L1 = rd_varint(j.in, p), L2 = rd_varint(j.in, p);
     const uint64_t st[3] = {p, p + L1, p + L1 + L2};
     for (int k = 0; k < 3 && ok; k++) {
       uint64_t q = st[k];
-      if (q + 5 > j.size || j.in[q] != 0x10 || j.in[q + 1] != 0 || j.in[q + 2] != 0 || j.in[q + 3] != 0 || j.in[q + 4] != 0x10) {
-        ok = false; err = (q + 5 <= j.size && j.in[q] == 0x10) ? 2 : 1;   // -s>=1 predictor tiles: unsupported
-        break;
+      GenLayer& gl = g.L[k];
+      if (q + 5 > j.size) { ok = false; break; }
+      if (j.in[q] != 0x10) { ok = false; err = (j.in[q] & 0xef) ? 2 : 1; break; }   // compaction / no prediction
+      gl.xt = (uint32_t)j.in[q + 1] + 1; gl.yt = (uint32_t)j.in[q + 2] + 1;
+      if (gl.xt == 1 && gl.yt == 1) {                           // layer_decode.hpp:203-209: one mask, no map
+        gl.nmask = 1;
+        gl.masks[0] = (uint16_t)((j.in[q + 3] << 8) | j.in[q + 4]);
+        if (gl.masks[0] != 0x0010) general = true;
+        q += 5;
+      } else {                                                  // :210-229: mask list, then the map stream
+        general = true;
+        gl.mapped = 1;
+        gl.nmask = j.in[q + 3];
+        q += 4;
+        if (gl.nmask < 1 || gl.nmask > 16 || q + 2 * (uint64_t)gl.nmask > j.size) { ok = false; break; }
+        for (uint32_t m = 0; m < gl.nmask; m++, q += 2) gl.masks[m] = (uint16_t)((j.in[q] << 8) | j.in[q + 1]);
+        if (gl.xt * gl.yt > HOH_GEN_MAPCAP) { ok = false; err = 2; break; }
+        ok = parse_stream(j, q, gen_sid(j, t, 1 + k), gen_sym_off(j, t, 1 + k), lane);
+        if (ok && j.streams[gen_sid(j, t, 1 + k)].n != gl.xt * gl.yt) ok = false;   // a wrong map count
+        if (!ok) break;
       }
-      q += 5;
       ok = parse_stream(j, q, t * SK_PER_TILE + 3 + k, (size_t)(t * 3 + k) * j.plane_cap, lane);
-      const uint32_t depth = k ? 9 : 8;
+      const uint32_t depth = (k && ti.mode == 128) ? 9 : 8;
       if (ok && j.streams[t * SK_PER_TILE + 3 + k].range != (1u << depth)) ok = false;
+      if (ok && j.streams[t * SK_PER_TILE + 3 + k].n > npix) ok = false;
       // full-width tile plane without LZ copies: the blocked layout k_dunpred_fast reads
-      if (ok && lane == 0 && ti.w == 256 && j.blk_ok &&
-          j.streams[t * SK_PER_TILE + 3 + k].n == (uint32_t)ti.w * (uint32_t)ti.h)
+      if (ok && !general && lane == 0 && ti.w == 256 && j.blk_ok &&
+          j.streams[t * SK_PER_TILE + 3 + k].n == npix)
         j.streams[t * SK_PER_TILE + 3 + k].blk = 1;
     }
   }
   if (!ok && !err) err = 1;
   if (lane == 0) {
+    if (ok && general) {                                        // k_dgen reads flat planes
+      for (int k = 0; k < 3; k++) j.streams[t * SK_PER_TILE + 3 + k].blk = 0;
+      j.gen[t] = g;
+    }
+    ti.gen = ok && general ? 1u : 0u;
     ti.err = err;
     j.tiles[t] = ti;
     if (err) atomicOr(j.gerr, err == 2 ? 2u : 1u);
@@ -1365,7 +1419,11 @@ __global__ __launch_bounds__(64) void k_dlz(DecJob j) {
   const uint16_t* bb = j.dsym + st[2].out_off;
   uint32_t* mt = j.matches + (size_t)t * 4 * (j.lz_cap + 1);
   const uint32_t npix = (uint32_t)ti.w * ti.h, w = (uint32_t)ti.w;
-  const uint32_t nf = st[0].n, gcap = min(min(st[1].n, st[2].n), j.lz_cap);
+  // a general tile's fourth stream holds the distances' high bytes (un_lz.hpp:160)
+  const bool four = ti.gen && j.gen[t].nlz == 4;
+  const DecStream s4 = four ? j.streams[gen_sid(j, t, 0)] : st[2];
+  const uint16_t* bb2 = j.dsym + s4.out_off;
+  const uint32_t nf = st[0].n, gcap = min(min(min(st[1].n, st[2].n), s4.n), j.lz_cap);
   const uint64_t lt = (1ull << lane) - 1;
   uint32_t idx0 = 0, g0 = 0, nuked0 = 0, xrow = 0;
   bool bad = false;
@@ -1378,7 +1436,7 @@ __global__ __launch_bounds__(64) void k_dlz(DecJob j) {
     uint32_t L = 0, back = 0;
     if (m) {
       if (g >= gcap) bad = true;
-      else { L = (uint32_t)len[g] + 4; back = bb[g]; }
+      else { L = (uint32_t)len[g] + 4; back = four ? (uint32_t)bb[g] | ((uint32_t)bb2[g] << 8) : (uint32_t)bb[g]; }
     }
     const uint32_t c = v + L;                                   // 255 entries: v = 255, L = 0
     const uint32_t ic = wave_incl_u32(c, lane), il = wave_incl_u32(L, lane);
@@ -1405,7 +1463,7 @@ __global__ __launch_bounds__(64) void k_dlz(DecJob j) {
   // copies that keep reading the row above make the wavefront serial: such tiles (and every LZ
   // tile narrower than 64, whose copies reach two rows up) are chain tiles (the chain role of k_dunpred_lz),
   // listed by width class; the others are k_dunpred_lz's work list
-  if (bad) return;
+  if (bad || ti.gen) return;                 // general tiles: k_dgen walks the match list itself
   if (!g0) {                                 // no copies: the planes must be whole (k_dunpred_fast)
     const uint32_t np = (uint32_t)ti.w * ti.h;
     if (st[3].n != np || st[4].n != np || st[5].n != np) { j.tiles[t].err = 1; atomicOr(j.gerr, 1u); }
@@ -1428,7 +1486,7 @@ __device__ __forceinline__ uint16_t dmed16(uint16_t a, uint16_t b, uint16_t c) {
 __device__ __forceinline__ bool unpred_fast(const DecJob& j, int t, const DecTile& ti) {
   const DecStream* st = j.streams + (size_t)t * SK_PER_TILE + 3;
   const uint32_t np = (uint32_t)ti.w * ti.h;
-  return ti.nmatch == 0 && st[0].n == np && st[1].n == np && st[2].n == np;
+  return !ti.gen && ti.nmatch == 0 && st[0].n == np && st[1].n == np && st[2].n == np;
 }
 
 // lane r gets v of lane r-1; lane 0 gets `old` (DPP wave_shr:1, bound_ctrl off)
@@ -2336,6 +2394,184 @@ __device__ __forceinline__ void compose_tile(const DecJob& j, int t) {
   }
 }
 
+// ---------------------------------------------------------------- general tiles
+// k_dgen: the inverse of channelpredict_all with LZ copies (unprediction.hpp:6-91) for every plane
+// of every general tile, then the tile's RGB.  A pixel's prediction needs its left neighbour's
+// value AND best predictor (row y's first pixel that of row y-1's last pixel), so a plane is one
+// serial chain of w * h steps: the parallelism is tiles x planes, one wave each.  The wave is the
+// chain's register file and its memory system: 64 pixels of a row per batch, lane l holding pixel
+// x0 + l -- its T / TL / TR from the row above (LDS), its residual (the copies' ballot gives the
+// residual index), its copy source when that lies before the batch, the best predictor of the pixel
+// above and the mask of the cell below, all loaded 64 wide before the chain runs.  The chain then
+// takes 64 steps of pure VALU work (every lane computes step i from its own registers and the
+// uniform L / best-left of step i - 1; lane i's result is the step's, broadcast by readlane), with
+// no memory access but the in-batch copies' lane permute; the batch's values leave as one 128-B
+// line.  k_unpredict_all's one-thread form of the same walk (gen_plane_serial; what-if EXP & 128 of
+// knob builds) is the yardstick it is measured against.
+__device__ __forceinline__ uint32_t gen_depth(const DecTile& ti, int p) { return (p && ti.mode == 128) ? 9u : 8u; }
+
+__device__ void gen_plane_serial(const DecJob& j, int t, const DecTile& ti, const GenLayer& gl, const uint16_t* lmask,
+                                 const uint16_t* res, const uint16_t* map, uint16_t* outp, uint16_t* top, uint8_t* bp,
+                                 uint32_t depth) {
+  const uint32_t w = ti.w, h = ti.h, c = 1u << depth, half = c >> 1;
+  const uint32_t ctw = (w + gl.xt - 1) / gl.xt, cth = (h + gl.yt - 1) / gl.yt;
+  const uint32_t* mt = j.matches + (size_t)t * 4 * (j.lz_cap + 1);
+  const uint32_t nm = ti.nmatch;
+  const bool med_only = !gl.mapped && gl.masks[0] == 0x0010;
+  for (uint32_t i = 0; i < w; i++) { bp[i] = 4; top[i] = (uint16_t)half; }
+  uint32_t k = 0, mi = 0;
+  for (uint32_t y = 0; y < h; y++) {
+    uint32_t L = half, TL = half;
+    for (uint32_t x = 0; x < w; x++) {
+      const uint32_t loc = y * w + x;
+      const uint32_t T = top[x], TR = top[x + 1 == w ? 0 : x + 1];
+      Preds P;
+      preds16(L, T, TL, TR, true, P);
+      while (mi < nm && mt[4 * mi] + mt[4 * mi + 1] <= loc) mi++;
+      const uint32_t back = (mi < nm && loc >= mt[4 * mi]) ? mt[4 * mi + 2] : 0u;
+      uint32_t v;
+      if (back) {
+        v = outp[loc - back];
+      } else {
+        const uint32_t pr = midp(pick(P, bp[x]), pick(P, bp[x == 0 ? w - 1 : x - 1]));
+        v = ((uint32_t)res[k++] - c - half + pr) & (c - 1);
+      }
+      outp[loc] = (uint16_t)v;
+      TL = T;
+      top[x] = (uint16_t)v;
+      L = v;
+      const uint32_t mk = gl.mapped ? lmask[map[((y + 1) / cth) * gl.xt + x / ctw]] : lmask[0];
+      bp[x] = med_only ? (uint8_t)4 : y + 1 < h ? (uint8_t)best_pred(v, P, mk, (int)c) : (uint8_t)0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void k_dgen(DecJob j) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dg_lds[];
+  if (dec_abort(j)) return;
+  const int t = blockIdx.x / 3, p = blockIdx.x % 3;
+  const DecTile ti = j.tiles[t];
+  if (ti.err || !ti.gen) return;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t w = ti.w, h = ti.h, npix = w * h;
+  uint16_t* prev = (uint16_t*)dg_lds;                        // the row above (this row's, behind the batch)
+  uint16_t* mrow = prev + j.tw;                              // the mask of the cell below, per column
+  uint16_t* lmask = mrow + j.tw;                             // the layer's masks
+  uint8_t* bpr = (uint8_t*)(lmask + 16);                     // best predictor of the pixel above
+  const GenLayer gl = j.gen[t].L[p];
+  const uint32_t depth = gen_depth(ti, p), c = 1u << depth, half = c >> 1;
+  const DecStream rs = j.streams[t * SK_PER_TILE + 3 + p];
+  const uint16_t* res = j.dsym + rs.out_off;
+  const uint32_t nres = rs.n;
+  const uint16_t* map = j.dsym + gen_sym_off(j, t, 1 + p);
+  uint16_t* outp = j.dplane + (size_t)(t * 3 + p) * j.npix_cap;
+  const uint32_t* mt = j.matches + (size_t)t * 4 * (j.lz_cap + 1);
+  const uint32_t nm = ti.nmatch;
+  const uint32_t ctw = (w + gl.xt - 1) / gl.xt, cth = (h + gl.yt - 1) / gl.yt;
+  // the -s0 layer (channelpredict_fastpath, prediction.hpp:6-41) inside a general tile
+  const bool med_only = !gl.mapped && gl.masks[0] == 0x0010;
+  {
+    // a map index that is not below the mask count, a residual count that is not the pixels
+    // outside the copies: corrupt
+    bool bad = false;
+    if (gl.mapped) for (uint32_t i = lane; i < gl.xt * gl.yt; i += 64) bad |= map[i] >= gl.nmask;
+    const uint32_t nuked = nm ? mt[4 * (nm - 1) + 3] + mt[4 * (nm - 1) + 1] : 0u;
+    bad |= nuked >= npix || nres != npix - nuked;
+    if (__any(bad)) {
+      if (lane == 0) { j.tiles[t].err = 1; atomicOr(j.gerr, 1u); }
+      return;
+    }
+  }
+  if (lane < 16) lmask[lane] = j.gen[t].L[p].masks[lane];
+  for (uint32_t i = lane; i < w; i += 64) { prev[i] = (uint16_t)half; bpr[i] = 4; }
+  __syncthreads();
+  if (j.exp & 128) {                                         // what-if EXP & 128: the one-thread walk (yardstick)
+    if (lane == 0) gen_plane_serial(j, t, ti, gl, lmask, res, map, outp, prev, bpr, depth);
+  } else {
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t mi = 0, mp = nm ? mt[0] : 0xffffffffu, ml = nm ? mt[1] : 0u, mb = nm ? mt[2] : 0u;   // the next match
+    uint32_t nk = 0;                                         // copied pixels before the batch
+    uint32_t Lc = half, bB = 4, first_v = half, tl_carry = half;
+    for (uint32_t y = 0; y < h; y++) {
+      if (y + 1 < h && (y == 0 || (y + 1) % cth == 0)) {     // row y + 1 enters a new row of cells
+        const uint32_t cy = (y + 1) / cth;
+        for (uint32_t x = lane; x < w; x += 64) mrow[x] = gl.mapped ? lmask[map[cy * gl.xt + x / ctw]] : lmask[0];
+        __syncthreads();
+      }
+      for (uint32_t x0 = 0; x0 < w; x0 += 64) {
+        const uint32_t x = x0 + lane, q0 = y * w + x0, q = q0 + lane;
+        const uint32_t nb = min(64u, w - x0);
+        const bool in = lane < nb;
+        // the batch's copies: the match list is sorted and disjoint (k_dlz)
+        uint32_t back = 0;
+        while (mp < q0 + nb) {
+          if (in && q >= mp && q < mp + ml) back = mb;
+          if (mp + ml > q0 + nb) break;                      // runs on into the next batch
+          mi++;
+          if (mi < nm) { const uint4 m4 = *(const uint4*)(mt + 4 * mi); mp = m4.x; ml = m4.y; mb = m4.z; }
+          else mp = 0xffffffffu;
+        }
+        const uint64_t cpm = __ballot(back != 0);
+        const uint32_t kidx = q - nk - (uint32_t)__popcll(cpm & below);
+        nk += (uint32_t)__popcll(cpm);
+        const bool inb = back && q - back >= q0;             // the source lies in this batch
+        const uint64_t inbm = __ballot(inb);
+        uint32_t r = 0, cpv = 0, srcl = lane;
+        if (in && !back) r = res[min(kidx, nres - 1)];
+        if (back) { if (inb) srcl = q - back - q0; else cpv = outp[q - back]; }
+        const uint32_t T = in ? prev[x] : 0u;
+        const uint32_t TL = lane ? (in ? (uint32_t)prev[x - 1] : 0u) : (x0 ? tl_carry : half);
+        const uint32_t TRs = (in && x + 1 < w) ? (uint32_t)prev[x + 1] : T;
+        const uint32_t bA = in ? bpr[x] : 0u;
+        const uint32_t mk = (in && y + 1 < h) ? mrow[x] : 0u;
+        const bool lastcol = x + 1 == w && w > 1;            // TR: this row's first value (top_row[0])
+        tl_carry = prev[x0 + nb - 1];
+        if (x0 == 0) Lc = half;
+        uint32_t v = 0, best = 0;
+        for (uint32_t i = 0; i < nb; i++) {
+          Preds P;
+          preds16(Lc, T, TL, lastcol ? first_v : TRs, true, P);
+          uint32_t cand;
+          if ((cpm >> i) & 1) {
+            cand = ((inbm >> i) & 1) ? (uint32_t)__shfl((int)v, (int)srcl) : cpv;
+          } else {
+            const uint32_t pr = midp(pick(P, bA), pick(P, bB));
+            cand = (r - c - half + pr) & (c - 1);           // unprediction.hpp:67-68 in uint16, % c
+          }
+          // the last row keeps 0 (prediction.hpp:214-216); a 1x1 0x0010 layer is MED on every row
+          const uint32_t bn = med_only ? 4u : y + 1 < h ? best_pred(cand, P, mk, (int)c) : 0u;
+          if (lane == i) { v = cand; best = bn; }
+          Lc = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)i);
+          bB = (uint32_t)__builtin_amdgcn_readlane((int)bn, (int)i);
+          if (x0 == 0 && i == 0) first_v = Lc;
+        }
+        __syncthreads();                                     // the batch's LDS reads are done
+        if (in) { prev[x] = (uint16_t)v; bpr[x] = (uint8_t)best; outp[q] = (uint16_t)v; }
+        __threadfence_block();                               // later batches' copies read outp
+        __syncthreads();
+      }
+    }
+  }
+  // the tile's RGB, by the wave that finishes its plane last (GenTile.pad counts them)
+  __threadfence();
+  uint32_t done = 0;
+  if (lane == 0) done = atomicAdd(&j.gen[t].pad, 1u);
+  done = (uint32_t)__shfl((int)done, 0);
+  if (done != 2) return;
+  __threadfence();
+  const uint16_t* G = j.dplane + (size_t)(t * 3) * j.npix_cap;
+  const uint16_t* Rp = G + j.npix_cap;
+  const uint16_t* Bp = Rp + j.npix_cap;
+  const uint32_t add = ti.mode == 128 ? 1u : 0u;             // sub-green planes (channel.hpp:73-79) or plain RGB
+  for (uint32_t i = lane; i < npix; i += 64) {
+    const uint32_t yy = i / w, xx = i - yy * w;
+    uint8_t* o = j.rgb + ((size_t)(ti.y0 + yy) * j.W + ti.x0 + xx) * 3;
+    const uint32_t g = G[i];
+    o[0] = (uint8_t)(Rp[i] + add * g); o[1] = (uint8_t)g; o[2] = (uint8_t)(Bp[i] + add * g);   // - 256: mod 256
+  }
+}
+static size_t dgen_smem(int tw) { return (size_t)tw * 5 + 32 + 16; }
+
 // ---------------------------------------------------------------- host side
 
 static int dbuf(DecWork& w, int k, size_t bytes, void** p) {
@@ -2659,15 +2895,19 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     if (j.blk_ok) j.plane_cap = std::max<uint32_t>(j.plane_cap, (uint32_t)(((size_t)j.th + 63) / 64 * BLK_BAND));
   }
   const int S = j.ntiles * SK_PER_TILE;
+  // General tiles (DecTile.gen): the enqueue-only calls never read the parse back, so their stream
+  // slots (SX behind the S the side index matches on), symbols and layer records are sized up front
+  const int SX = j.ntiles * HOH_GEN_XS, S2 = S + SX;
   DecWork& w = ctx_dec(c);
   void* q;
   int e;
   if ((e = dbuf(w, 0, (size_t)j.ntiles * sizeof(DecTile), &q))) return e; j.tiles = (DecTile*)q;
-  if ((e = dbuf(w, 1, (size_t)S * sizeof(DecStream), &q))) return e; j.streams = (DecStream*)q;
+  if ((e = dbuf(w, 1, (size_t)S2 * sizeof(DecStream), &q))) return e; j.streams = (DecStream*)q;
   j.cum_stride = 513;
-  if ((e = dbuf(w, 2, (size_t)S * 513 * 4, &q))) return e; j.cum = (uint32_t*)q;
-  if ((e = dbuf(w, 3, (size_t)S * 512 * 2, &q))) return e; j.bsym = (uint16_t*)q;
-  if ((e = dbuf(w, 4, ((size_t)j.ntiles * 3 * j.plane_cap + (size_t)j.ntiles * 3 * j.lz_cap) * 2, &q))) return e; j.dsym = (uint16_t*)q;
+  if ((e = dbuf(w, 2, (size_t)S2 * 513 * 4, &q))) return e; j.cum = (uint32_t*)q;
+  if ((e = dbuf(w, 3, (size_t)S2 * 512 * 2, &q))) return e; j.bsym = (uint16_t*)q;
+  if ((e = dbuf(w, 4, ((size_t)j.ntiles * 3 * j.plane_cap + (size_t)j.ntiles * 3 * j.lz_cap + (size_t)j.ntiles * gen_sym_per_tile(j)) * 2, &q))) return e; j.dsym = (uint16_t*)q;
+  if ((e = dbuf(w, 8, (size_t)j.ntiles * sizeof(GenTile), &q))) return e; j.gen = (GenTile*)q;
   if ((e = dbuf(w, 5, (size_t)j.ntiles * 4 * (j.lz_cap + 1) * 4, &q))) return e; j.matches = (uint32_t*)q;
   if ((e = dbuf(w, 6, 64, &q))) return e; j.gerr = (uint32_t*)q;
   if ((e = dbuf(w, 7, (size_t)j.ntiles * 3 * j.npix_cap * 2, &q))) return e; j.dplane = (uint16_t*)q;
@@ -2688,7 +2928,7 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   j.nix = index_nstreams(idx);
   const int indexed = j.ix && j.nix == S;
   if (hipMemsetAsync(j.gerr, 0, 64, s) != hipSuccess) return 3;
-  if (hipMemsetAsync(j.streams, 0, (size_t)S * sizeof(DecStream), s) != hipSuccess) return 3;
+  if (hipMemsetAsync(j.streams, 0, (size_t)S2 * sizeof(DecStream), s) != hipSuccess) return 3;
   ctx_mark(c, s, "start", as == nullptr);
   const int nfile = j.nimg > 1 ? j.nimg : 1;
   if (as && as->hl) hipLaunchKernelGGL(k_dhdr, dim3(nfile), dim3(64), 0, s, j, as->hdr[0], as->hdr[1], as->hl);
@@ -2734,6 +2974,15 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   }
   ctx_mark(c, s, "drans", false);
   if (!indexed) hipLaunchKernelGGL(k_dstored, dim3(S), dim3(256), 0, s, j, S);
+  {
+    // general tiles' extra streams (fourth LZ stream, predictor maps: short), one wave each
+    DecJob jx = j;
+    jx.streams = j.streams + S;
+    jx.cum = j.cum + (size_t)S * j.cum_stride;
+    jx.bsym = j.bsym + (size_t)S * 512;
+    hipLaunchKernelGGL(k_drans_wave, dim3(SX), dim3(64), DL_SMEM, s, jx, SX, 0);
+    hipLaunchKernelGGL(k_dstored, dim3(SX), dim3(256), 0, s, jx, SX);
+  }
   hipLaunchKernelGGL(k_dlz, dim3(j.ntiles), dim3(64), 0, s, j);
   ctx_mark(c, s, "dlz", false);
   // chain tiles: their back-distance maps (the chains themselves run inside k_dunpred_lz)
@@ -2773,6 +3022,8 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     hipLaunchKernelGGL(k_dcompose, dim3(gsmall), dim3(256), 0, s, j);   // the chain tiles' RGB
   }
   ctx_mark(c, s, "dunpred", false);
+  hipLaunchKernelGGL(k_dgen, dim3(3 * j.ntiles), dim3(64), dgen_smem(j.tw), s, j);   // general tiles
+  ctx_mark(c, s, "dgen", false);
   if (hipGetLastError() != hipSuccess) return 3;
   if (as) {
     launch_status_dec(j.gerr, as->bytes, as->status, s, j.nimg > 1 ? j.nimg : 1);

@@ -284,6 +284,7 @@ __device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring) {
     if (!s_notgrey && ti.colours != -1 && ti.colours <= 2) fl |= TF_BINARY;
     if (!s_notgrey && !(fl & TF_BINARY)) fl |= TF_UNREPRODUCIBLE;   // choh.cpp:196-205 copies garbage
     if (s_notgrey && ti.colours != -1) fl |= TF_PALETTE_CAND;
+    if (j.decodable) fl = 0;       // grey / bitimage / indexed tiles carry no pixel data (Q15): sub-green or RGB only
     ti.flags = fl;
     ti.nmatch = 0;
     ti.ncand = (uint32_t)s_ncand;
@@ -721,6 +722,7 @@ __global__ __launch_bounds__(NT) void k_front256(EncodeJob j) {
     if (!s_notgrey && ti.colours != -1 && ti.colours <= 2) fl |= TF_BINARY;
     if (!s_notgrey && !(fl & TF_BINARY)) fl |= TF_UNREPRODUCIBLE;   // choh.cpp:196-205 copies garbage
     if (s_notgrey && ti.colours != -1) fl |= TF_PALETTE_CAND;
+    if (j.decodable) fl = 0;       // grey / bitimage / indexed tiles carry no pixel data (Q15): sub-green or RGB only
     ti.flags = fl;
     ti.nmatch = 0;
     ti.ncand = (uint32_t)s_ncand;

@@ -322,6 +322,15 @@ __global__ __launch_bounds__(64) void k_tables(EncodeJob j, SidMap sm) {
     mx = carry;
     return sum;
   };
+  // HOH_OPT_DECODABLE: the raw table packs every frequency into maxbits bits (Q4), so a frequency
+  // of 2^maxbits or more is lost and the stream cannot be read back (a predictor map over 5 masks
+  // at prob_bits 8: always).  Such a stream takes the clamped table instead.
+  bool raw_lossy = false;
+  if (j.decodable) {
+    uint32_t fmx = 0;
+    for (uint32_t i = lane; i < range; i += 64) fmx = max(fmx, fr[i]);
+    raw_lossy = (wave_max_u32(fmx) >> maxbits) != 0;
+  }
   uint32_t lo_x[16] = {0}, up_x[16] = {0}, climb, climb2, sbf1, sbf2, mf, mb;
   const uint64_t s1 = scan(1, first, lo_x, climb, sbf1, mf);
   const uint64_t s2 = scan(-1, lastnz, up_x, climb2, sbf2, mb);
@@ -337,7 +346,7 @@ __global__ __launch_bounds__(64) void k_tables(EncodeJob j, SidMap sm) {
     }
     exp_cl += (uint64_t)sbf2 * ((uint64_t)climb2 - (uint64_t)climb - 1);     // size_t wrap (Q5)
     exp_cl = (exp_cl + 8 - 1) / 8;
-    const bool raw = expected_raw < exp_cl;
+    const bool raw = expected_raw < exp_cl && !raw_lossy;
     hd[vlen] = (uint8_t)((1u << 7) + (pb << 2) + (raw ? 1 : 2));
     s_mode = raw ? 1 : 2;
   }

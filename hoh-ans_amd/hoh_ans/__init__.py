@@ -190,11 +190,16 @@ class Context:
     def set_option(self, option, value):
         """hoh_ctx_set_option: e.g. set_option(OPT_NOIX_DECODER, NOIX_LANES)."""
         check(lib().hoh_ctx_set_option(self.h, option, value), "hoh_ctx_set_option")
+        if option == OPT_DECODABLE:
+            self.decodable = int(value)
 
 
 # hoh_ctx_set_option (include/hoh_ans.h)
 OPT_NOIX_DECODER = 1
 NOIX_ADAPTIVE, NOIX_LANES, NOIX_MULTI, NOIX_WAVE = -1, 0, 1, 2
+# 1: every encode of the context (any speed, hoh_layer_encode included) writes files that decode;
+# 0 (default): the reference's bytes, whose -s1..-s4 layers cannot be read back (SURVEY Q14)
+OPT_DECODABLE = 2
 
 
 _CTX = None
@@ -520,13 +525,23 @@ class MultiGPU:
 
 # ------------------------------------------------------------------ host-buffer API (reference names)
 
-def choh(rgb, ctx=None, speed=0):
-    """`choh in out W H -sN` on an (H, W, 3) uint8 array -> (file bytes, printed size)."""
+def choh(rgb, ctx=None, speed=0, decodable=None):
+    """`choh in out W H -sN [--decodable]` on an (H, W, 3) uint8 array -> (file bytes, printed size).
+    decodable=True / False sets OPT_DECODABLE for this call (the context's setting comes back after
+    it); None leaves the context as it is."""
     import torch
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
     H, W, _ = rgb.shape
     d = torch.from_numpy(rgb.reshape(-1)).cuda()
-    out, n, printed = encode_image(d, W, H, ctx=ctx, speed=speed)
+    ctx = ctx or default_ctx()
+    was = getattr(ctx, "decodable", 0)
+    if decodable is not None:
+        ctx.set_option(OPT_DECODABLE, 1 if decodable else 0)
+    try:
+        out, n, printed = encode_image(d, W, H, ctx=ctx, speed=speed)
+    finally:
+        if decodable is not None:
+            ctx.set_option(OPT_DECODABLE, was)
     torch.cuda.synchronize()
     return out[:n].cpu().numpy().tobytes(), printed
 

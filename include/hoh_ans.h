@@ -34,8 +34,13 @@ extern "C" {
                                    (grey non-binary tiles, choh.cpp:196-205; palette prefix
                                    longer than the indexed layer, choh.cpp:301-308)             */
 #define HOH_E_UNSUPPORTED 6     /* valid but not implemented on this path (4-channel formats);
-                                   decoder: indexed (mode 127) tiles, which carry no palette
-                                   (SURVEY Q15), and -s>=1 layers (Q14)                         */
+                                   decoder: grey / bitimage / indexed (mode 127) tiles, which
+                                   carry no pixel data or no palette, nested tiling,
+                                   compaction layers, predictor maps of more than 4096 cells.
+                                   -s>=1 files written WITHOUT HOH_OPT_DECODABLE are parsed like
+                                   any other file now: their stale layers (Q14) read as
+                                   HOH_E_CORRUPT, or decode to wrong pixels where the stale
+                                   stream happens to parse                                      */
 #define HOH_E_CORRUPT 7         /* decoder: malformed or undecodable bitstream (incl. the
                                    reference's lossy raw tables)                     */
 #define HOH_E_NODEV 8           /* no GPU / HIP device unavailable                              */
@@ -73,6 +78,26 @@ void hoh_reset_kernel_stats(hoh_ctx* ctx);
 #define HOH_NOIX_LANES 0
 #define HOH_NOIX_MULTI 1
 #define HOH_NOIX_WAVE 2
+/* HOH_OPT_DECODABLE (0 default, 1): every encode entry point of the context, hoh_layer_encode
+ * included, writes files that can be read back at any speed.  At 0 the files are the reference's
+ * byte for byte, whose -s1..-s4 layers announce a predictor map and then carry a truncated prefix of
+ * a stale stream.  At 1:
+ *  - a layer is its header, its map stream and ONE whole entropy stream of the residuals the header
+ *    describes (at -s>=1 with a grid larger than 1x1 the searched, LZ-cleaned residuals, otherwise
+ *    the MED residuals).  With s(pb) the stream's size at prob_bits pb, the candidates are 16, 17,
+ *    18, 19 if s(16) < s(15), else 15, 14, 13, 12, and the layer takes the first candidate of
+ *    strictly smallest size (the reference ladder's own evaluation set, layer_encode.hpp:326-392);
+ *    -s0 layers stay MED at prob_bits 15;
+ *  - a tile is sub-green (mode 128) unless, at -s>=3, the three plain planes sum strictly smaller
+ *    (RGB, mode 2, choh.cpp:309); the grey, bitimage and indexed modes carry no decodable pixel
+ *    data (Q15) and are never taken, so HOH_E_UNREPRODUCIBLE cannot arise;
+ *  - the vertical LZ search stops at distance 65535: the reference's 65536 does not fit the two
+ *    distance bytes and reads back as 0 (lz.hpp:55, :85-87);
+ *  - no stream (hoh_encode_entropy included) takes the raw frequency table where it would drop a
+ *    frequency's high bits (Q4: a predictor map over a few masks always would); it takes the
+ *    clamped table instead.
+ * Not covered: hoh_mgpu_* (its contexts are its own) and header-only (untiled, Q13) files. */
+#define HOH_OPT_DECODABLE 2
 int hoh_ctx_set_option(hoh_ctx* ctx, int option, int64_t value);
 
 /* ---- image level: `choh in out W H -sN` / `dhoh in out` -------------------------------- */
@@ -84,8 +109,9 @@ size_t hoh_encode_bound(int W, int H);
  * W*H*3 interleaved RGB bytes from d_rgb, writes the exact bytes choh writes (header-only for
  * untiled images) to d_out.  *out_size = bytes written; *printed (optional) = the
  * number choh prints (choh.cpp:522).  -s1..-s4 run the predictor search, seek-distance LZ and
- * prob_bits ladder (layer_encode.hpp:122-392); their files are undecodable by construction
- * (SURVEY Q14), so they get no side index. */
+ * prob_bits ladder (layer_encode.hpp:122-392) and get no side index.  Without HOH_OPT_DECODABLE
+ * their files are the reference's, undecodable by construction; with it they read
+ * back through every decode entry point. */
 int hoh_encode_image(hoh_ctx* ctx, const uint8_t* d_rgb, int W, int H, int speed,
                      uint8_t* d_out, size_t cap, size_t* out_size, size_t* printed, void* stream);
 
@@ -103,7 +129,15 @@ int hoh_encode_image_ix(hoh_ctx* ctx, const uint8_t* d_rgb, int W, int H, int sp
                         hoh_index* idx, void* stream);
 
 /* Replaces dhoh.cpp:297-396 (with the decoder defects of SURVEY Q1, Q9-Q12 fixed).  d_hoh holds
- * `size` bytes of a .hoh file (as written by choh -s0); writes W*H*3 RGB bytes to d_rgb. */
+ * `size` bytes of a .hoh file; writes W*H*3 RGB bytes to d_rgb.  Every decode entry point reads,
+ * whoever wrote the file: tile modes 128 (sub-green) and 2 (RGB); LZ with three or four streams
+ * (distance = backby2 << 8 | backby, up to 65535); layers with a predictor map of any grid (up to
+ * 4096 cells), 1 to 16 masks of any value, a map stream and a residual stream, stored or rANS at
+ * prob_bits up to 19 (16..19 are read from five bits of the metadata byte: the reference's writer
+ * carries them into bit 6, its reader masks that bit off).  A wrong map or residual count, a map
+ * index that is not below the mask count, or truncation gives HOH_E_CORRUPT.  An -s>=1 file
+ * written without HOH_OPT_DECODABLE carries stale layers (Q14): HOH_E_CORRUPT, or wrong pixels
+ * where the stale stream happens to parse. */
 int hoh_decode_image(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, uint8_t* d_rgb, size_t cap,
                      int* W, int* H, void* stream);
 int hoh_decode_image_ix(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, uint8_t* d_rgb, size_t cap,
@@ -275,7 +309,8 @@ int hoh_encode_entropy_batch(hoh_ctx* ctx, const uint16_t* d_syms, const uint64_
 
 /* Replaces layer_encode(uint16_t*, size_t, int, int, int, size_t, uint8_t*, uint8_t*)
  * (layer_encode.hpp:11-20), cruncher_mode 0..4 (1..4: grid predictor search and prob_bits ladder,
- * with the reference's stale-prefix output).  nuke may be NULL (no LZ). */
+ * with the reference's stale-prefix output; on a HOH_OPT_DECODABLE context the layer
+ * hoh_layer_decode reads back).  nuke may be NULL (no LZ). */
 int hoh_layer_encode(hoh_ctx* ctx, const uint16_t* data, size_t size, int width, int height,
                      int depth, size_t cruncher_mode, const uint8_t* nuke, uint8_t* out,
                      size_t cap, size_t* written);

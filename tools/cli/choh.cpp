@@ -5,6 +5,8 @@
 // argv[5] unchecked when it is missing; here that is the documented default).
 // `--gpus N` / `--devices a,b,..` (tools/cli/gpus.h) encode over several GPUs in this one process
 // (hoh_mgpu_encode_image: a band of tile rows per device, one RCCL gather); same bytes.
+// `--decodable` (anywhere on the line) sets HOH_OPT_DECODABLE: the file differs from the
+// reference's at -s1..-s4 and can be read back by dhoh (one GPU only).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -26,7 +28,20 @@ static bool read_file(const char* path, std::vector<uint8_t>& b) {
 }
 
 int main(int argc, char** argv) {
+  bool decodable = false;
+  {
+    int w = 1;
+    for (int i = 1; i < argc; i++) {
+      if (!std::strcmp(argv[i], "--decodable")) decodable = true;
+      else argv[w++] = argv[i];
+    }
+    argc = w;
+  }
   const std::vector<int> devices = take_devices(argc, argv);
+  if (decodable && devices.size() > 1) {
+    std::printf("--decodable encodes on one GPU\n");
+    return 1;
+  }
   if (argc < 5) {
     std::printf("not enough arguments\nusage: choh infile.rgb outfile.hoh width height -s0\n");
     return 1;
@@ -52,6 +67,7 @@ int main(int argc, char** argv) {
   const int dev0 = devices.empty() ? 0 : devices[0];   // --devices 3 / one entry: that GPU
   hoh_mgpu* mg = nullptr;
   int r = devices.size() > 1 ? hoh_mgpu_create(&mg, (int)devices.size(), devices.data()) : hoh_ctx_create(&ctx, dev0);
+  if (r == HOH_OK && decodable) r = hoh_ctx_set_option(ctx, HOH_OPT_DECODABLE, 1);
   if (r != HOH_OK) { std::fprintf(stderr, "choh: %s\n", hoh_strerror(r)); return r; }
   const size_t cap = hoh_encode_bound(W, H);
   uint8_t *d_in = nullptr, *d_out = nullptr;
