@@ -4,6 +4,7 @@
 // entry point returns HOH_E_NODEV.
 #include "hoh_internal.h"
 #include "hoh_dec.h"
+#include "hoh_index_blob.h"
 #include "../../include/hoh_ans.h"
 
 #include <math.h>
@@ -54,6 +55,13 @@ struct hoh_index {
   size_t ck_count = 0;
   int nimg = 1;                 // a batch's index: its image count and file stride (payload
   uint64_t stride = 0;          //   offsets are absolute in the batch buffer)
+  // Host copy of the stream records, for the entry points that need sizes on the host (serialize,
+  // concat).  Loaded, built and concatenated indexes have it from the start; an encode records
+  // its index on the device only, so the copy is fetched when first asked for.
+  std::vector<IndexStream> host;
+  bool host_ok = true;
+  Buf stage;                    // serialize: destination offsets, then the packed checkpoints
+  int device = -1;              // device of the buffers (set when they are first reserved)
 };
 
 struct Scratch {                // see ScratchFrame (hoh_dec.h)
@@ -590,7 +598,7 @@ int hoh_encode_tiles_speed(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int s
                            uint8_t* d_out, size_t cap, uint32_t* d_tile_sizes, size_t* out_size, hoh_index* idx,
                            void* stream) {
   if (!c || !d_rgb || !d_out || !out_size || W <= 0 || H <= 0 || speed < 0 || speed > 4) return HOH_E_ARG;
-  if (speed && idx) idx->nstreams = 0;
+  if (speed && idx) index_clear(idx);
   (void)hipSetDevice(c->device);
   int xt, yt, tw, th;
   if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) return HOH_E_ARG;
@@ -606,7 +614,7 @@ int hoh_encode_tiles_async(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int s
                            void* stream) {
   if (!c || !d_rgb || !d_out || !d_tile_sizes || !d_status || W <= 0 || H <= 0 || speed < 0 || speed > 4)
     return HOH_E_ARG;
-  if (speed && idx) idx->nstreams = 0;
+  if (speed && idx) index_clear(idx);
   (void)hipSetDevice(c->device);
   int xt, yt, tw, th;
   if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) return HOH_E_ARG;
@@ -649,7 +657,7 @@ int hoh_encode_tiles_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W
   }
   if ((int64_t)rows * n > (1ll << 30) || (int64_t)ntiles * n > (1 << 24)) return HOH_E_ARG;
   (void)hipSetDevice(c->device);
-  if (speed && idx) idx->nstreams = 0;                 // -s>=1 files get no side index
+  if (speed && idx) index_clear(idx);                 // -s>=1 files get no side index
   // -s>=1 workspaces are ~8 MB per tile: stacks of at most speed_stack() tiles, one after another
   const int per = speed ? std::max(1, speed_stack() / ntiles) : n;
   for (int i0 = 0; i0 < n; i0 += per) {
@@ -684,7 +692,7 @@ int hoh_encode_image_ix(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int spee
   if (tiled) {
     launch_put_bytes(d_out, hb, (int)hl, s);      // the header, ahead of the tiles (one host sync per call)
     r = encode_tiles_impl(c, d_rgb, W, H, 0, xt * yt, d_out, cap, hl, 1, nullptr, &total, idx, s, speed);
-    if (speed && idx) idx->nstreams = 0;
+    if (speed && idx) index_clear(idx);
     *out_size = (size_t)total;
     if (printed) *printed = (size_t)total;
   } else {
@@ -698,7 +706,7 @@ int hoh_encode_image_ix(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int spee
     if (r == HOH_OK && hipStreamSynchronize(s) != hipSuccess) r = HOH_E_HIP;
     *out_size = hl;
     if (printed) *printed = hl + (size_t)total;
-    if (idx) idx->nstreams = 0;
+    if (idx) index_clear(idx);
   }
   return r;
 }
@@ -715,7 +723,7 @@ int hoh_encode_image_async(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int s
   hb[hl++] = (uint8_t)(xt - 1);
   hb[hl++] = (uint8_t)(yt - 1);
   if (cap < hl) return HOH_E_CAP;
-  if (speed && idx) idx->nstreams = 0;
+  if (speed && idx) index_clear(idx);
   launch_put_bytes(d_out, hb, (int)hl, s);
   uint64_t total = 0;
   return encode_tiles_impl(c, d_rgb, W, H, 0, xt * yt, d_out, cap, hl, 1, nullptr, &total, speed ? nullptr : idx, s,
@@ -747,7 +755,7 @@ int hoh_encode_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int 
   hb[hl++] = (uint8_t)(yt - 1);
   if (stride < hl) return HOH_E_CAP;
   launch_put_bytes(d_out, hb, (int)hl, s, n, stride);
-  if (speed && idx) idx->nstreams = 0;                 // -s>=1 files get no side index
+  if (speed && idx) index_clear(idx);                 // -s>=1 files get no side index
   // -s>=1 workspaces are ~8 MB per tile: stacks of at most speed_stack() tiles, one after another
   const int per = speed ? std::max(1, speed_stack() / (xt * yt)) : n;
   for (int i0 = 0; i0 < n; i0 += per) {
@@ -946,6 +954,7 @@ void hoh_index_destroy(hoh_index* idx) {
   if (!idx) return;
   freebuf(idx->ck);
   freebuf(idx->streams);
+  freebuf(idx->stage);
   delete idx;
 }
 
@@ -955,9 +964,231 @@ size_t hoh_index_bytes(const hoh_index* idx) {
 
 }  // extern "C"
 
+// ---------------------------------------------------------------- side index persistence
+// (blob layout and validation: hoh_index_blob.h)
+static_assert(HOH_BLOB_SEG == HOH_SEG && HOH_BLOB_SPT == SK_PER_TILE && HOH_BLOB_RANS == SM_RANS,
+              "hoh_index_blob.h restates these without the HIP headers");
+
+// the stream records on the host.  `s` orders the copy behind the work that recorded the index;
+// without a stream the whole device is waited for
+static int index_host(const hoh_index* cidx, hipStream_t s) {
+  hoh_index* idx = const_cast<hoh_index*>(cidx);
+  if (idx->host_ok) return HOH_OK;
+  if (idx->device >= 0) (void)hipSetDevice(idx->device);
+  idx->host.resize((size_t)idx->nstreams);
+  const size_t bytes = (size_t)idx->nstreams * sizeof(IndexStream);
+  if (s) {
+    if (hipMemcpyAsync(idx->host.data(), idx->streams.p, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return HOH_E_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return HOH_E_HIP;
+  } else {
+    if (hipDeviceSynchronize() != hipSuccess) return HOH_E_HIP;
+    if (hipMemcpy(idx->host.data(), idx->streams.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) return HOH_E_HIP;
+  }
+  idx->host_ok = true;
+  return HOH_OK;
+}
+
+static uint32_t rec_nseg(const IndexStream& x) { return x.mode == SM_RANS ? (x.n + HOH_SEG - 1) / HOH_SEG : 0u; }
+
+// stream order: where each stream's first checkpoint goes; returns the total
+static uint64_t canon_offsets(const std::vector<IndexStream>& h, uint64_t base, uint32_t* off) {
+  uint64_t run = base;
+  for (size_t s = 0; s < h.size(); s++) { off[s] = (uint32_t)run; run += rec_nseg(h[s]); }
+  return run;
+}
+
+extern "C" {
+
+size_t hoh_index_serialized_size(const hoh_index* idx) {
+  if (!idx || index_host(idx, nullptr) != HOH_OK) return 0;
+  uint64_t nck = 0;
+  for (const IndexStream& x : idx->host) nck += rec_nseg(x);
+  return HOH_BLOB_HDR + idx->host.size() * HOH_BLOB_REC + (size_t)nck * HOH_BLOB_CK;
+}
+
+int hoh_index_serialize(const hoh_index* cidx, uint8_t* out, size_t cap, size_t* written, void* stream) {
+  if (!cidx || !written || (!out && cap)) return HOH_E_ARG;
+  hoh_index* idx = const_cast<hoh_index*>(cidx);
+  hipStream_t s = (hipStream_t)stream;
+  int e;
+  if ((e = index_host(idx, s))) return e;
+  const size_t S = idx->host.size();
+  std::vector<uint32_t> off(S + 1);
+  const uint64_t nck = canon_offsets(idx->host, 0, off.data());
+  const size_t need = HOH_BLOB_HDR + S * HOH_BLOB_REC + (size_t)nck * HOH_BLOB_CK;
+  *written = need;
+  if (cap < need) return HOH_E_CAP;
+  memset(out, 0, HOH_BLOB_HDR + S * HOH_BLOB_REC);
+  memcpy(out, "HOHX", 4);
+  blob_put32(out + 4, HOH_BLOB_VERSION);
+  blob_put32(out + 8, HOH_SEG);
+  blob_put32(out + 12, (uint32_t)S);
+  blob_put32(out + 16, S ? (uint32_t)idx->nimg : 1u);
+  blob_put64(out + 24, S && idx->nimg > 1 ? idx->stride : 0);
+  blob_put64(out + 32, nck);
+  for (size_t k = 0; k < S; k++) {
+    const IndexStream& x = idx->host[k];
+    uint8_t* r = out + HOH_BLOB_HDR + k * HOH_BLOB_REC;
+    blob_put32(r + 12, x.mode);
+    if (x.mode != SM_RANS) continue;                       // every other field stays zero
+    blob_put64(r, x.payload_off);
+    blob_put32(r + 8, x.n);
+    blob_put32(r + 16, x.words);
+  }
+  if (!nck) return HOH_OK;
+  if (idx->device >= 0) (void)hipSetDevice(idx->device);
+  if (!s && hipDeviceSynchronize() != hipSuccess) return HOH_E_HIP;
+  const size_t offb = rup(S * 4, 16);
+  if ((e = ensure(idx->stage, offb + (size_t)nck * HOH_BLOB_CK))) return e;
+  uint8_t* st = (uint8_t*)idx->stage.p;
+  if (hipMemcpyAsync(st, off.data(), S * 4, hipMemcpyHostToDevice, s) != hipSuccess) return HOH_E_HIP;
+  launch_index_pack((const IndexStream*)idx->streams.p, (const Checkpoint*)idx->ck.p, (const uint32_t*)st, (int)S,
+                    st + offb, 1, s);
+  if (hipGetLastError() != hipSuccess) return HOH_E_HIP;
+  if (hipMemcpyAsync(out + HOH_BLOB_HDR + S * HOH_BLOB_REC, st + offb, (size_t)nck * HOH_BLOB_CK, hipMemcpyDeviceToHost,
+                     s) != hipSuccess)
+    return HOH_E_HIP;
+  return hipStreamSynchronize(s) == hipSuccess ? HOH_OK : HOH_E_HIP;
+}
+
+int hoh_index_deserialize(hoh_index* idx, const uint8_t* blob, size_t size, void* stream) {
+  if (!idx) return HOH_E_ARG;
+  index_clear(idx);
+  BlobHeader h;
+  if (!blob_validate(blob, size, &h)) return HOH_E_CORRUPT;   // before any HIP call
+  if (!h.nstreams) return HOH_OK;
+  std::vector<IndexStream> hs(h.nstreams);
+  std::vector<Checkpoint> hc((size_t)h.nck);
+  uint64_t run = 0;
+  for (uint32_t k = 0; k < h.nstreams; k++) {
+    const uint8_t* r = blob_rec(blob, k);
+    IndexStream x;
+    memset(&x, 0, sizeof(x));
+    x.payload_off = blob_u64(r);
+    x.n = blob_u32(r + 8);
+    x.mode = blob_u32(r + 12);
+    x.words = blob_u32(r + 16);
+    x.ckpt_off = (uint32_t)run;                             // widx_end 0: wi is the word index itself
+    run += rec_nseg(x);
+    hs[k] = x;
+  }
+  for (uint64_t k = 0; k < h.nck; k++) {
+    const uint8_t* p = blob_ck(blob, h, k);
+    Checkpoint c;
+    c.xl = blob_u32(p); c.xh = blob_u32(p + 4); c.widx = blob_u32(p + 8); c.pad = 0;
+    hc[(size_t)k] = c;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int e = index_reserve(idx, hs.size(), hc.size());
+  if (!e && hipMemcpyAsync(idx->streams.p, hs.data(), hs.size() * sizeof(IndexStream), hipMemcpyHostToDevice, s) != hipSuccess)
+    e = HOH_E_HIP;
+  if (!e && !hc.empty() &&
+      hipMemcpyAsync(idx->ck.p, hc.data(), hc.size() * sizeof(Checkpoint), hipMemcpyHostToDevice, s) != hipSuccess)
+    e = HOH_E_HIP;
+  if (!e && hipStreamSynchronize(s) != hipSuccess) e = HOH_E_HIP;   // the host copies go away
+  if (e) return e;
+  idx->nstreams = (int)h.nstreams;
+  idx->ck_count = hc.size();
+  idx->nimg = (int)h.nimg;
+  idx->stride = h.stride;
+  idx->host.swap(hs);
+  idx->host_ok = true;
+  return HOH_OK;
+}
+
+int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream) {
+  if (!dst || n <= 0 || !src) return HOH_E_ARG;
+  for (int i = 0; i < n; i++)
+    if (!src[i] || src[i] == dst || src[i]->nstreams != src[0]->nstreams || (src[i]->nstreams && src[i]->nimg != 1))
+      return HOH_E_ARG;
+  if (n > 1 && stride == 0) return HOH_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t S = (size_t)src[0]->nstreams;
+  if (S * (size_t)n > 0x7fffffffull) return HOH_E_ARG;
+  index_clear(dst);
+  if (!S) return HOH_OK;
+  int e;
+  for (int i = 0; i < n; i++)
+    if ((e = index_host(src[i], s))) return e;
+  if (src[0]->device >= 0) (void)hipSetDevice(src[0]->device);
+  if (!s && hipDeviceSynchronize() != hipSuccess) return HOH_E_HIP;
+  std::vector<IndexStream> hs(S * n);
+  std::vector<uint32_t> off(S * n);
+  uint64_t run = 0;
+  for (int i = 0; i < n; i++) {
+    run = canon_offsets(src[i]->host, run, off.data() + S * i);
+    for (size_t k = 0; k < S; k++) {
+      const IndexStream& a = src[i]->host[k];
+      IndexStream x;
+      memset(&x, 0, sizeof(x));
+      x.mode = a.mode;
+      if (a.mode == SM_RANS) {
+        x.payload_off = a.payload_off + (uint64_t)i * (n > 1 ? stride : 0);
+        x.n = a.n;
+        x.words = a.words;
+        x.ckpt_off = off[S * i + k];
+      }
+      hs[S * i + k] = x;
+    }
+  }
+  if (run > 0xffffffffull) return HOH_E_ARG;
+  if ((e = index_reserve(dst, hs.size(), (size_t)run))) return e;
+  if ((e = ensure(dst->stage, off.size() * 4))) return e;
+  if (hipMemcpyAsync(dst->stage.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) return HOH_E_HIP;
+  for (int i = 0; i < n; i++)
+    launch_index_pack((const IndexStream*)src[i]->streams.p, (const Checkpoint*)src[i]->ck.p,
+                      (const uint32_t*)dst->stage.p + S * i, (int)S, dst->ck.p, 0, s);
+  if (hipGetLastError() != hipSuccess) return HOH_E_HIP;
+  if (hipMemcpyAsync(dst->streams.p, hs.data(), hs.size() * sizeof(IndexStream), hipMemcpyHostToDevice, s) != hipSuccess)
+    return HOH_E_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return HOH_E_HIP;
+  dst->nstreams = (int)hs.size();
+  dst->ck_count = (size_t)run;
+  dst->nimg = n;
+  dst->stride = n > 1 ? stride : 0;
+  dst->host.swap(hs);
+  dst->host_ok = true;
+  return HOH_OK;
+}
+
+int hoh_index_build(hoh_ctx* c, const uint8_t* d_hoh, size_t size, hoh_index* idx, int* W, int* H, void* stream) {
+  if (!c || !d_hoh || !idx) return HOH_E_ARG;
+  index_clear(idx);
+  (void)hipSetDevice(c->device);
+  int w = 0, h = 0;
+  const int r = index_build_impl(c, d_hoh, size, idx, &w, &h, pick(c, stream));
+  if (W) *W = w;
+  if (H) *H = h;
+  if (r) index_clear(idx);
+  return r;
+}
+
+}  // extern "C"
+
+void index_clear(hoh_index* idx) {
+  idx->nstreams = 0;
+  idx->ck_count = 0;
+  idx->nimg = 1;
+  idx->stride = 0;
+  idx->host.clear();
+  idx->host_ok = true;
+}
+
+IndexStream* index_stream_buf(hoh_index* idx) { return (IndexStream*)idx->streams.p; }
+
+int index_commit(hoh_index* idx, int nstreams, size_t nck, hipStream_t s) {
+  idx->nstreams = nstreams;
+  idx->ck_count = nck;
+  idx->nimg = 1;
+  idx->stride = 0;
+  idx->host_ok = false;
+  return index_host(idx, s);
+}
+
 // index capture: copy every plane stream's checkpoints + payload location (device to device)
 int index_reserve(hoh_index* idx, size_t nstreams, size_t nck) {
   int e;
+  if (idx->device < 0 && hipGetDevice(&idx->device) != hipSuccess) idx->device = -1;
   if ((e = ensure(idx->streams, nstreams * sizeof(IndexStream)))) return e;
   return ensure(idx->ck, nck * sizeof(Checkpoint));
 }
@@ -974,6 +1205,8 @@ int index_capture(hoh_index* idx, const EncodeJob& j, hipStream_t s) {
   idx->ck_count = (size_t)S * per;
   idx->nimg = j.nimg > 1 ? j.nimg : 1;
   idx->stride = j.nimg > 1 ? j.out_stride : 0;
+  idx->host.clear();                        // the records exist on the device only (index_host)
+  idx->host_ok = false;
   launch_index_capture(j, (IndexStream*)idx->streams.p, per, s);
   return hipGetLastError() == hipSuccess ? HOH_OK : HOH_E_HIP;
 }

@@ -68,6 +68,14 @@ void launch_index_capture(const EncodeJob& j, IndexStream* is, size_t per, hipSt
 const IndexStream* index_streams(const hoh_index* idx);
 const Checkpoint* index_ckpts(const hoh_index* idx);
 int index_nstreams(const hoh_index* idx);
+void index_clear(hoh_index* idx);                          // the empty index: no streams, nimg 1, stride 0
+IndexStream* index_stream_buf(hoh_index* idx);
+// a built index (k_decode.hip, index_build_impl): nstreams records and nck checkpoints are in
+// place on the device, in the compact layout; copies the records to the host
+int index_commit(hoh_index* idx, int nstreams, size_t nck, hipStream_t s);
+void launch_index_pack(const IndexStream* is, const Checkpoint* ck, const uint32_t* dst_off, int nstreams, void* dst,
+                       int rec12, hipStream_t s);
+int index_build_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, hoh_index* idx, int* Wp, int* Hp, hipStream_t s);
 int index_batch(const hoh_index* idx, uint64_t* stride);    // images and file stride the index was recorded for
 DecWork& ctx_dec(hoh_ctx* c);
 hipStream_t ctx_stream(hoh_ctx* c, void* s);

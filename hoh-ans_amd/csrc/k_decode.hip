@@ -1380,6 +1380,333 @@ __global__ __launch_bounds__(64) void k_drans_lanes(DecJob j, const uint32_t* li
   }
 }
 
+// ---------------------------------------------------------------- side index for any file
+// hoh_index_build: the decoder's own front (k_dtable, k_dparse), then the serial chains walked
+// once more without their symbols: k_ibuild_lanes is k_drans_lanes' schedule (rounds packed by
+// k_dlpack, compact tables, one lane per chain, 16-word payload rings refilled a group ahead) with
+// a chain that keeps no 64-symbol output line and stores, before symbol k * HOH_SEG, the 16-byte
+// Checkpoint {xl, xh, wi} -- 256 stores per 65,536-step plane chain, none of them awaited.  The
+// record is the decoder's state before that symbol, which is the encoder's after coding it
+// (k_rans_enc.hip, ckpt), so a built index equals the recorded one.
+#define IB_NCK 11                // gerr word: checkpoints of the built index
+
+// Stream records of the index (compact layout: stream s's checkpoints at the running sum of
+// ceil(n / HOH_SEG) over the rANS streams before it) from the parsed streams; refuses what the
+// indexed k_drans would skip.  One workgroup.
+__global__ __launch_bounds__(1024) void k_ibscan(DecJob j, int nstreams, IndexStream* is) {
+  if (dec_abort(j)) return;
+  __shared__ uint64_t wsum[17];
+  const int tid = threadIdx.x;
+  uint64_t carry = 0;
+  for (int s0 = 0; s0 < nstreams; s0 += 1024) {
+    const int s = s0 + tid;
+    IndexStream x;
+    memset(&x, 0, sizeof(x));
+    uint32_t nseg = 0;
+    if (s < nstreams) {
+      const DecStream d = j.streams[s];
+      if (s % SK_PER_TILE == 0 && j.tiles[s / SK_PER_TILE].gen) atomicOr(j.gerr, 2u);   // general tile
+      x.mode = d.mode;
+      if (d.mode == SM_RANS) {
+        if (d.range > 512 || d.pb > 15) atomicOr(j.gerr, 2u);
+        x.payload_off = d.payload_off;
+        x.n = d.n;
+        x.words = d.words;
+        nseg = (d.n + DSEG - 1) / DSEG;
+      }
+    }
+    uint64_t tot;
+    const uint64_t incl = block_scan_1024(nseg, wsum, &tot);
+    if (s < nstreams) {
+      x.ckpt_off = (uint32_t)(carry + incl - nseg);
+      is[s] = x;
+    }
+    carry += tot;
+  }
+  if (tid == 0) j.gerr[IB_NCK] = (uint32_t)carry;
+}
+
+// dm_chain_t without the symbols: the whole chain of stream d, its state recorded in ck[k] before
+// symbol k * HOH_SEG.  Same payload ring, same bounds (every fetch inside j.size), same end checks.
+template <class Step, class Look>
+__device__ __forceinline__ bool ib_chain_t(const DecJob& j, const DecStream& d, Checkpoint* ck, Step step, Look look) {
+  const uint32_t t4 = (uint32_t)threadIdx.x * 4;
+  const uint32_t pb = d.pb, mask = (1u << pb) - 1;
+  const uint64_t P = d.payload_off;
+  const uint32_t al = (uint32_t)(P & 3);
+  const uint64_t szal = j.size & ~3ull;
+  uint32_t tailw = 0;
+  for (uint64_t q = szal; q < j.size; q++) tailw |= (uint32_t)j.in[q] << (8 * (q & 3));
+  auto fetch5 = [&](uint32_t kw, uint32_t* A) {              // raw dwords covering words kw .. kw+3
+    const uint64_t a = (P & ~3ull) + (uint64_t)kw * 4;
+    if (a + 20 <= szal) {
+      typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));
+      const u4a v = *(const u4a*)(j.in + a);
+      A[0] = v.x; A[1] = v.y; A[2] = v.z; A[3] = v.w;
+      A[4] = *(const uint32_t*)(j.in + a + 16);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 5; e++) {
+        const uint64_t b = a + 4 * e;
+        A[e] = b + 4 <= szal ? *(const uint32_t*)(j.in + b) : (b == szal ? tailw : 0u);
+      }
+    }
+  };
+  auto put4 = [&](uint32_t kw, const uint32_t* A) {
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+      lds_st32(t4 | (((kw + e) & (DR_RW - 1)) << 8), __builtin_amdgcn_alignbyte(A[e + 1], A[e], al));
+  };
+  auto record = [&](uint32_t k, uint32_t xh, uint32_t xl, uint32_t wi) {
+    Checkpoint c;
+    c.xl = xl; c.xh = xh; c.widx = wi; c.pad = 0;
+    ck[k] = c;
+  };
+  uint32_t wi = 2, xh, xl;
+  {
+    uint32_t A[5];
+    fetch5(0, A);
+    xl = __builtin_amdgcn_alignbyte(A[1], A[0], al);
+    xh = __builtin_amdgcn_alignbyte(A[2], A[1], al);         // Rans64DecInit
+  }
+  const uint32_t ngrp = pb >= 7 ? d.n >> 6 : 0;               // 64-symbol groups, four per checkpoint
+  if (ngrp) {
+    uint32_t fill = wi, pend[5];
+    bool hp = true;                                          // pend holds words fill .. fill+3
+    {
+      uint32_t a0[5], a1[5];
+      fetch5(fill, a0); fetch5(fill + 4, a1);
+      put4(fill, a0); put4(fill + 4, a1);
+      fill += 8;
+      fetch5(fill, pend);
+    }
+    for (uint32_t g = 0; g < ngrp; g++) {
+      if ((g & (DSEG / 64 - 1)) == 0) record(g / (DSEG / 64), xh, xl, wi);
+#pragma unroll
+      for (int gi = 0; gi < 4; gi++) {
+        if (hp) { put4(fill, pend); fill += 4; }
+        while (fill - wi < 8) {
+          uint32_t t[5];
+          fetch5(fill, t); put4(fill, t); fill += 4;
+        }
+        hp = fill + 4 - wi <= DR_RW;
+        if (hp) fetch5(fill, pend);
+#pragma unroll
+        for (int u = 0; u < 16; u++) {
+          const uint32_t w = lds_u32(t4 | ((wi & (DR_RW - 1)) << 8));
+          (void)step(xh, xl, w, wi);
+        }
+      }
+    }
+  }
+  // the last n % 64 symbols (or a whole stream with prob_bits < 7): one step at a time, payload
+  // words from the file
+  uint64_t x = ((uint64_t)xh << 32) | xl;
+  for (uint32_t i = ngrp * 64; i < d.n; i++) {
+    if ((i & (DSEG - 1)) == 0) record(i / DSEG, (uint32_t)(x >> 32), (uint32_t)x, wi);
+    const uint32_t slot = (uint32_t)x & mask;
+    uint32_t sym, c, f;
+    look(slot, sym, c, f);
+    x = (uint64_t)f * (x >> pb) + (slot - c);                // Rans64DecAdvance
+    if (x < (1ull << 31)) {
+      if (wi >= d.words) return false;
+      x = (x << 32) | ld_u32_unaligned(j.in, P + (uint64_t)wi * 4);
+      wi++;
+    }
+  }
+  return x == (1ull << 31) && wi <= d.words;
+}
+
+// k_drans_lanes' rounds with ib_chain_t as the chain (tables built the same way)
+__global__ __launch_bounds__(64) void k_ibuild_lanes(DecJob j, const uint32_t* list, int nlist, const uint32_t* tbytes,
+                                                     uint32_t budget, const uint32_t* rounds, const IndexStream* is,
+                                                     Checkpoint* ck) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t dm_lds[];
+  const int lane = threadIdx.x;
+  uint32_t* scr = dm_lds + DL_SCR / 4;
+  if (lane == 0) {
+    scr[0] = *(volatile const uint32_t*)j.gerr;
+    scr[1] = *(volatile const uint32_t*)(j.gerr + 5);
+    scr[2] = *(volatile const uint32_t*)(j.gerr + DL_NR);
+  }
+  __syncthreads();
+  if (scr[0]) return;
+  const uint32_t cl = scr[1], nr = scr[2];
+  auto entry = [&](uint32_t i) -> uint32_t { return i < cl ? list[i] : list[nlist - 1 - (i - cl)]; };
+  for (uint32_t r = blockIdx.x; r < nr; r += gridDim.x) {
+    const uint32_t p = rounds[r], n = rounds[r + 1] - p;
+    const uint32_t sz = (uint32_t)lane < n ? tbytes[entry(p + lane)] : 0u;
+    uint32_t incl = sz;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t u = __shfl_up(incl, o);
+      if (lane >= o) incl += u;
+    }
+    const uint32_t tb = DL_TAB + incl - sz;
+    for (uint32_t m = 0; m < n; m++) {
+      const uint32_t sid = entry(p + m);
+      const DecStream d = j.streams[sid];
+      const uint32_t* cum = j.cum + (size_t)sid * j.cum_stride;
+      const uint32_t Bb = __shfl(tb, (int)m), Eb = Bb + ((dl_nb(d.pb) * 2 + 7) & ~7u);
+      uint32_t pres = 0, cv[9];
+#pragma unroll
+      for (int e = 0; e < 9; e++) cv[e] = 8 * lane + e <= d.range ? cum[8 * lane + e] : 0;
+#pragma unroll
+      for (int e = 0; e < 8; e++)
+        if (8 * lane + e < d.range && cv[e + 1] > cv[e]) pres |= 1u << e;
+      const uint32_t c = __popc(pres);
+      uint32_t incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+      }
+      const uint32_t P = __shfl(incl, 63);
+      uint32_t k = incl - c;
+      for (int e = 0; e < 8; e++) {
+        if (!((pres >> e) & 1)) continue;
+        const uint32_t sv = 8 * lane + e, c0 = cv[e], c1 = cv[e + 1];
+        lds_st2(Eb + 8 * k, make_uint2(c0 | (sv << 16), c1 - c0));
+        for (uint32_t b = (c0 + (1u << DL_BSH) - 1) >> DL_BSH; b <= (c1 - 1) >> DL_BSH; b++) lds_st16(Bb + 2 * b, k);
+        k++;
+      }
+      if (lane < 3) lds_st2(Eb + 8 * (P + lane), make_uint2(0xffffu, 0u));
+    }
+    __syncthreads();
+    if ((uint32_t)lane < n) {
+      const uint32_t sid = entry(p + lane);
+      const DecStream d = j.streams[sid];
+      const uint32_t pb = d.pb, mask = (1u << pb) - 1, Bb = tb, Eb = tb + ((dl_nb(pb) * 2 + 7) & ~7u);
+      const bool ok = ib_chain_t(
+          j, d, ck + is[sid].ckpt_off,
+          [&](uint32_t& xh, uint32_t& xl, uint32_t nw, uint32_t& wi) { return dstep_l(Bb, Eb, mask, pb, xh, xl, nw, wi); },
+          [&](uint32_t slot, uint32_t& sym, uint32_t& c, uint32_t& f) {
+            uint32_t a = Eb + (lds_u16(Bb + ((slot >> DL_BSH) << 1)) << 3);
+            uint2 t = lds_u2(a);
+            for (;;) {
+              const uint2 u = lds_u2(a + 8);
+              if ((u.x & 0xffffu) > slot) break;
+              t = u;
+              a += 8;
+            }
+            sym = t.x >> 16;
+            c = t.x & 0xffffu;
+            f = t.y;
+          });
+      if (!ok) atomicOr(j.gerr, 4u);
+    }
+    __syncthreads();                                         // the tables are rebuilt next round
+  }
+}
+
+// k_drans_multi's rounds (full DrTables, 12 chains per CU, the shorter step) with ib_chain_t as
+// the chain: what a build takes while the plane chains fit one round and the device is its own,
+// as a no-index decode does (decode_run)
+template <int MS>
+__global__ __launch_bounds__(64) void k_ibuild_multi(DecJob j, const uint32_t* list, int nlist, const IndexStream* is,
+                                                     Checkpoint* ck) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t dm_lds[];
+  const int lane = threadIdx.x;
+  uint32_t* scr = dm_lds + DM_SCR / 4;
+  if (lane == 0) {
+    scr[0] = *(volatile const uint32_t*)j.gerr;
+    scr[1] = *(volatile const uint32_t*)(j.gerr + 5);
+    scr[2] = *(volatile const uint32_t*)(j.gerr + 6);
+  }
+  __syncthreads();
+  if (scr[0]) return;
+  const uint32_t cl = scr[1], total = scr[1] + scr[2];
+  auto entry = [&](uint32_t i) -> uint32_t { return i < cl ? list[i] : list[nlist - 1 - (i - cl)]; };
+  for (uint32_t base = blockIdx.x * MS; base < total; base += gridDim.x * MS) {
+    const int ns = (int)min((uint32_t)MS, total - base);
+    for (int m = 0; m < ns; m++) {
+      const DecStream d = j.streams[entry(base + m)];
+      const uint32_t nb = ((1u << d.pb) + 31) >> 5;
+      uint2* bk = (uint2*)((unsigned char*)dm_lds + dm_bk(m));
+      for (uint32_t b = lane; b < nb; b += 64) bk[b] = make_uint2(0, 0);
+    }
+    __syncthreads();
+    for (int m = 0; m < ns; m++) {
+      const uint32_t sid = entry(base + m);
+      const DecStream d = j.streams[sid];
+      const uint32_t* cum = j.cum + (size_t)sid * j.cum_stride;
+      uint2* bk = (uint2*)((unsigned char*)dm_lds + dm_bk(m));
+      uint2* sy = (uint2*)((unsigned char*)dm_lds + dm_sy(MS, m));
+      uint32_t pres = 0, cv[9];
+#pragma unroll
+      for (int e = 0; e < 9; e++) cv[e] = 8 * lane + e <= d.range ? cum[8 * lane + e] : 0;
+#pragma unroll
+      for (int e = 0; e < 8; e++)
+        if (8 * lane + e < d.range && cv[e + 1] > cv[e]) pres |= 1u << e;
+      const uint32_t c = __popc(pres);
+      uint32_t incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+      }
+      uint32_t k = incl - c;
+      for (int e = 0; e < 8; e++) {
+        if (!((pres >> e) & 1)) continue;
+        const uint32_t sv = 8 * lane + e, c0 = cv[e], c1 = cv[e + 1];
+        sy[k] = make_uint2(c1 - c0, c0 | (sv << 16));
+        for (uint32_t b = (c0 + 31) >> 5; b <= (c1 - 1) >> 5; b++) bk[b].y = k;
+        if (c0 & 31) atomicOr(&bk[c0 >> 5].x, 1u << (c0 & 31));
+        k++;
+      }
+    }
+    __syncthreads();
+    if (lane < ns) {
+      const uint32_t sid = entry(base + lane);
+      const DecStream d = j.streams[sid];
+      const uint32_t bkb = dm_bk(lane), syb = dm_sy(MS, lane);
+      const uint32_t pb = d.pb, mask = (1u << pb) - 1, bmask = (mask >> 2) & ~7u;
+      DrTables tb;
+      tb.bk = (uint2*)((unsigned char*)dm_lds + bkb);
+      tb.sy = (uint2*)((unsigned char*)dm_lds + syb);
+      const bool ok = ib_chain_t(
+          j, d, ck + is[sid].ckpt_off,
+          [&](uint32_t& xh, uint32_t& xl, uint32_t nw, uint32_t& wi) { return dstep_m(bkb, syb, bmask, mask, pb, xh, xl, nw, wi); },
+          [&](uint32_t slot, uint32_t& sym, uint32_t& c, uint32_t& f) { tb.lookup(slot, sym, c, f); });
+      if (!ok) atomicOr(j.gerr, 4u);
+    }
+    __syncthreads();                                         // the tables are rebuilt next round
+  }
+}
+
+// the rANS streams k_dmlist leaves out (prob_bits < 7: at most 64 slots, short): one plain lane
+// each, symbols found by walking the global cumulative table
+__global__ __launch_bounds__(64) void k_ibuild_plain(DecJob j, int nstreams, const IndexStream* is, Checkpoint* ck) {
+  if (dec_abort(j)) return;
+  const int sid = blockIdx.x * 64 + threadIdx.x;
+  if (sid >= nstreams) return;
+  const DecStream d = j.streams[sid];
+  if (d.mode != SM_RANS || d.range > 512 || d.pb >= 7) return;
+  const uint32_t* cum = j.cum + (size_t)sid * j.cum_stride;
+  Checkpoint* o = ck + is[sid].ckpt_off;
+  const uint32_t pb = d.pb, mask = (1u << pb) - 1;
+  uint64_t x = (uint64_t)ld_u32_unaligned(j.in, d.payload_off) | ((uint64_t)ld_u32_unaligned(j.in, d.payload_off + 4) << 32);
+  uint32_t wi = 2;
+  for (uint32_t i = 0; i < d.n; i++) {
+    if ((i & (DSEG - 1)) == 0) {
+      Checkpoint c;
+      c.xl = (uint32_t)x; c.xh = (uint32_t)(x >> 32); c.widx = wi; c.pad = 0;
+      o[i / DSEG] = c;
+    }
+    const uint32_t slot = (uint32_t)x & mask;
+    uint32_t sy = 0;
+    while (cum[sy + 1] <= slot && sy + 1 < d.range) sy++;
+    const uint32_t c0 = cum[sy], f = cum[sy + 1] - c0;
+    x = (uint64_t)f * (x >> pb) + (slot - c0);               // Rans64DecAdvance
+    if (x < (1ull << 31)) {
+      if (wi >= d.words) { atomicOr(j.gerr, 4u); return; }
+      x = (x << 32) | ld_u32_unaligned(j.in, d.payload_off + (uint64_t)wi * 4);
+      wi++;
+    }
+  }
+  if (x != (1ull << 31)) atomicOr(j.gerr, 4u);
+}
+
 // stored streams: MSB-first fixed-width fields (the no-index path; with an index k_drans's
 // workgroup of the stream does this itself)
 __global__ void k_dstored(DecJob j, int nstreams) {
@@ -2673,7 +3000,7 @@ int decode_images_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stri
   if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;
   const size_t img = (size_t)W * H * 3;
   if (n == 1 || !batch_stacks(W, H)) {
-    if (idx && n > 1) return 6;
+    if (index_nstreams(idx) && n > 1) return 6;        // an empty index is no index
     for (int i = 0; i < n; i++) {
       const int r = decode_image_async_impl(c, d_in + i * stride, stride, W, H, d_rgb + i * img, img, idx,
                                             d_status + 2 * i, s);
@@ -2784,7 +3111,7 @@ int decode_tiles_images_async_impl(hoh_ctx* c, int n, const uint8_t* d_blob, siz
   const int y0 = (t0 / xt) * th, rows = std::min(H, (t0 + ntiles) / xt * th) - y0;
   const size_t band = (size_t)W * rows * 3;
   if (n == 1 || !batch_stacks(W, H)) {
-    if (idx && n > 1) return 6;
+    if (index_nstreams(idx) && n > 1) return 6;        // an empty index is no index
     for (int i = 0; i < n; i++) {
       const int r = decode_tiles_async_impl(c, d_blob + i * stride, stride, W, H, t0, ntiles, d_sizes + (size_t)i * ntiles,
                                             d_rgb + i * band - (size_t)y0 * W * 3, idx, d_status + 2 * i, s);
@@ -2918,7 +3245,7 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   if ((e = dbuf(w, 15, (size_t)j.ntiles * j.th * ((j.tw + 15) & ~15) + 16, &q))) return e; j.bmap = (uint8_t*)q;
 #endif
   j.lz_xrow = lz_xrow(j.nimg > 1);
-  if (idx) {                                   // a batch's index serves that batch's layout only
+  if (index_nstreams(idx)) {                   // a batch's index serves that batch's layout only (an empty one: any)
     uint64_t st = 0;
     const int ni = index_batch(idx, &st);
     if (ni != (j.nimg > 1 ? j.nimg : 1) || (ni > 1 && st != j.in_stride)) return 1;
@@ -3036,6 +3363,104 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   if (ge & 2) return 6;
   if (ge) return 7;
   return 0;
+}
+
+// hoh_index_build: header, tile table and stream parse exactly as decode_image_impl / decode_run
+// do them (same workspaces, so a decode on this context afterwards allocates nothing new for
+// them), then the records and the chains.  Synchronous.  6: a file the indexed decoder would not
+// decode in full (general, palette, grey or bitimage tiles, wide streams); 7: corrupt.
+int index_build_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, hoh_index* idx, int* Wp, int* Hp, hipStream_t s) {
+  uint8_t hb[16] = {0};
+  const size_t hn = size < 16 ? size : 16;
+  if (hipMemcpyAsync(hb, d_in, hn, hipMemcpyDeviceToHost, s) != hipSuccess) return 3;
+  if (hipStreamSynchronize(s) != hipSuccess) return 3;
+  if (hn < 8 || hb[0] != 153 || hb[1] != 72 || hb[2] != 79 || hb[3] != 72) return 7;
+  if (hb[4] != 2 || hb[5] != 8) return 6;
+  uint64_t p = 6, wv = 0, hv = 0;
+  for (uint64_t* v : {&wv, &hv}) {                           // varint.hpp:6-27 (at most 3 bytes each)
+    const uint64_t b0 = hb[p++];
+    if (!(b0 & 0x80)) { *v = b0; continue; }
+    const uint64_t b1 = hb[p++];
+    if (!(b1 & 0x80)) { *v = ((b0 & 0x7f) << 7) + b1; continue; }
+    *v = ((b0 & 0x7f) << 14) + ((b1 & 0x7f) << 7) + hb[p++];
+  }
+  const int W = (int)wv + 1, H = (int)hv + 1;
+  *Wp = W; *Hp = H;
+  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;   // header-only files (Q13)
+  DecJob j;
+  memset(&j, 0, sizeof(j));
+  j.W = W; j.H = H;
+  j.xt = W / 256; j.yt = H / 256;
+  j.tw = (W + j.xt - 1) / j.xt; j.th = (H + j.yt - 1) / j.yt;
+  if (p + 2 > size || hb[p] != (uint8_t)(j.xt - 1) || hb[p + 1] != (uint8_t)(j.yt - 1)) return 7;
+  j.prefix = p + 2;
+  j.ntiles = j.xt * j.yt;
+  j.in = d_in;
+  j.size = size;
+  j.npix_cap = (uint32_t)(((size_t)j.tw * j.th + 63) / 64 * 64);
+  j.lz_cap = (uint32_t)((j.npix_cap / 4 + j.npix_cap / 255 + 16 + 7) / 8 * 8);
+  j.plane_cap = (uint32_t)(((size_t)j.npix_cap + 8 * UP_P + 128 + 63) / 64 * 64);
+  j.blk_ok = j.tw == 256;
+  if (j.blk_ok) j.plane_cap = std::max<uint32_t>(j.plane_cap, (uint32_t)(((size_t)j.th + 63) / 64 * BLK_BAND));
+  const int S = j.ntiles * SK_PER_TILE, S2 = S + j.ntiles * HOH_GEN_XS;
+  const size_t per = j.npix_cap / HOH_SEG + 2;               // >= ceil(n / HOH_SEG) of any stream k_dparse accepts
+  if ((size_t)S * per > 0xffffffffull) return 6;
+  DecWork& w = ctx_dec(c);
+  void* q;
+  int e;
+  if ((e = dbuf(w, 0, (size_t)j.ntiles * sizeof(DecTile), &q))) return e; j.tiles = (DecTile*)q;
+  if ((e = dbuf(w, 1, (size_t)S2 * sizeof(DecStream), &q))) return e; j.streams = (DecStream*)q;
+  j.cum_stride = 513;
+  if ((e = dbuf(w, 2, (size_t)S2 * 513 * 4, &q))) return e; j.cum = (uint32_t*)q;
+  if ((e = dbuf(w, 3, (size_t)S2 * 512 * 2, &q))) return e; j.bsym = (uint16_t*)q;
+  if ((e = dbuf(w, 8, (size_t)j.ntiles * sizeof(GenTile), &q))) return e; j.gen = (GenTile*)q;
+  if ((e = dbuf(w, 6, 64, &q))) return e; j.gerr = (uint32_t*)q;
+  if ((e = dbuf(w, 13, (size_t)S * 12 + 8, &q))) return e;
+  uint32_t* mlist = (uint32_t*)q;
+  uint32_t* tbytes = mlist + S;
+  uint32_t* rounds = tbytes + S;
+  if ((e = index_reserve(idx, (size_t)S, (size_t)S * per))) return e;
+  IndexStream* is = index_stream_buf(idx);
+  Checkpoint* ck = index_ckpt_buf(idx);
+  if (hipMemsetAsync(j.gerr, 0, 64, s) != hipSuccess) return 3;
+  if (hipMemsetAsync(j.streams, 0, (size_t)S2 * sizeof(DecStream), s) != hipSuccess) return 3;
+  ctx_mark(c, s, "start", true);
+  hipLaunchKernelGGL(k_dtable, dim3(1), dim3(1024), 0, s, j);
+  ctx_mark(c, s, "dtable", false);
+  hipLaunchKernelGGL(k_dparse, dim3(j.ntiles), dim3(64), 0, s, j);
+  ctx_mark(c, s, "dparse", false);
+  hipLaunchKernelGGL(k_ibscan, dim3(1), dim3(1024), 0, s, j, S, is);
+  ctx_mark(c, s, "ibscan", false);
+  hipLaunchKernelGGL(k_dmlist, dim3((S + 255) / 256), dim3(256), 0, s, j, S, mlist);
+  // the chain kernel, chosen as decode_run chooses a no-index decode's (HOH_OPT_NOIX_DECODER)
+  const int pin = ctx_noix(c);
+  const bool one_round = 3 * j.ntiles <= DM_MS * ctx_cus(c);
+  const bool multi = pin == HOH_NOIX_MULTI || (pin != HOH_NOIX_LANES && one_round && !noix_busy(w, ctx_device(c)));
+  if (multi) {
+    const int nmax = std::min(S, 6 * j.ntiles);
+    const int grid = std::min((nmax + DM_MS - 1) / DM_MS, ctx_cus(c));
+    hipLaunchKernelGGL(k_ibuild_multi<DM_MS>, dim3(grid), dim3(64), dm_smem(DM_MS), s, j, (const uint32_t*)mlist, S,
+                       (const IndexStream*)is, ck);
+  } else {
+    hipLaunchKernelGGL(k_dlsize, dim3(S), dim3(64), 0, s, j, tbytes);
+    const uint32_t budget = dl_budget();
+    hipLaunchKernelGGL(k_dlpack, dim3(1), dim3(64), 0, s, j, (const uint32_t*)mlist, S, (const uint32_t*)tbytes, budget,
+                       rounds);
+    const int grid = std::min(S, dl_wg_per_cu() * ctx_cus(c));
+    hipLaunchKernelGGL(k_ibuild_lanes, dim3(grid), dim3(64), DL_TAB + budget, s, j, (const uint32_t*)mlist, S,
+                       (const uint32_t*)tbytes, budget, (const uint32_t*)rounds, (const IndexStream*)is, ck);
+  }
+  if (w.noix_ev) (void)hipEventRecord(w.noix_ev, s);
+  hipLaunchKernelGGL(k_ibuild_plain, dim3((S + 63) / 64), dim3(64), 0, s, j, S, (const IndexStream*)is, ck);
+  ctx_mark(c, s, "ibchains", false);
+  if (hipGetLastError() != hipSuccess) return 3;
+  uint64_t* host = ctx_pinned(c);
+  if (hipMemcpyAsync(host, j.gerr, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return 3;
+  if (hipStreamSynchronize(s) != hipSuccess) return 3;
+  const uint32_t* ge = (const uint32_t*)host;
+  if (ge[0] & 2) return 6;
+  if (ge[0]) return 7;
+  return index_commit(idx, S, ge[IB_NCK], s);
 }
 
 // ---------------------------------------------------------------- single stream (decode_entropy)

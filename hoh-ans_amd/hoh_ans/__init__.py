@@ -85,6 +85,11 @@ def lib():
                                              vp, vp]
         L.hoh_decode_tiles.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         for name, args in (
+            ("hoh_index_serialized_size", [vp]),
+            ("hoh_index_serialize", [vp, vp, sz, szp, vp]),
+            ("hoh_index_deserialize", [vp, C.c_char_p, sz, vp]),
+            ("hoh_index_build", [vp, vp, sz, vp, ip, ip, vp]),
+            ("hoh_index_concat", [vp, C.c_int, C.POINTER(vp), C.c_uint64, vp]),
             ("hoh_decode_image", [vp, vp, sz, vp, sz, ip, ip, vp]),
             ("hoh_decode_image_ix", [vp, vp, sz, vp, sz, ip, ip, vp, vp]),
             ("hoh_encode_image_async", [vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
@@ -120,6 +125,8 @@ def lib():
         ):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
+        if hasattr(L, "hoh_index_serialized_size"):
+            L.hoh_index_serialized_size.restype = sz
         if hasattr(L, "hoh_entropy_bound"):
             L.hoh_entropy_bound.restype = sz
             L.hoh_entropy_bound.argtypes = [sz, sz, C.c_uint32]
@@ -249,12 +256,58 @@ class Index:
     def nbytes(self):
         return lib().hoh_index_bytes(self.h)
 
+    def serialized_size(self):
+        return lib().hoh_index_serialized_size(self.h)
+
+    def to_bytes(self, ctx=None):
+        """hoh_index_serialize: the sidecar blob (layout in include/hoh_ans.h).  ctx: the context
+        whose stream recorded the index (the call is ordered behind it); None waits for the device."""
+        n = C.c_size_t(0)
+        s = vp(lib().hoh_ctx_stream(ctx.h)) if ctx is not None else None
+        r = lib().hoh_index_serialize(self.h, None, 0, C.byref(n), s)
+        if r not in (HOH_OK, 2):
+            raise HohError(r, "hoh_index_serialize")
+        out = np.empty(n.value, np.uint8)
+        check(lib().hoh_index_serialize(self.h, _p(out), out.size, C.byref(n), s), "hoh_index_serialize")
+        return out[:n.value].tobytes()
+
+    @classmethod
+    def from_bytes(cls, b):
+        """hoh_index_deserialize: HohError(E_CORRUPT) for anything but a well-formed blob."""
+        ix = cls()
+        b = bytes(b)
+        check(lib().hoh_index_deserialize(ix.h, b, len(b), None), "hoh_index_deserialize")
+        return ix
+
+    @classmethod
+    def concat(cls, indexes, stride):
+        """hoh_index_concat: the batch index of len(indexes) files laid out stride bytes apart."""
+        ix = cls()
+        hs = (vp * len(indexes))(*[i.h for i in indexes])
+        check(lib().hoh_index_concat(ix.h, len(indexes), hs, stride, None), "hoh_index_concat")
+        return ix
+
     def __del__(self):
         try:
             if self.h:
                 lib().hoh_index_destroy(self.h)
         except Exception:
             pass
+
+
+def build_index(hoh_dev, size, ctx=None, index=None):
+    """hoh_index_build: the side index of the .hoh in hoh_dev (a uint8 torch tensor in HBM, `size`
+    bytes), from the file alone.  Fills and returns `index` (a new Index when None); on HohError the
+    index passed in is left empty."""
+    import torch
+    ctx = ctx or default_ctx()
+    ix = index if index is not None else Index()
+    w, h = C.c_int(), C.c_int()
+    r = lib().hoh_index_build(ctx.h, vp(hoh_dev.data_ptr()), size, ix.h, C.byref(w), C.byref(h),
+                              _stream_ptr(torch, ctx))
+    _after_call(torch, ctx)
+    check(r, "hoh_index_build")
+    return ix
 
 
 def encode_image(rgb_dev, W, H, out_dev=None, ctx=None, index=None, speed=0):

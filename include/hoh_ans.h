@@ -72,7 +72,8 @@ void hoh_reset_kernel_stats(hoh_ctx* ctx);
  * chain with full tables while the decode has the device to itself, compact-table lanes beside
  * other no-index decodes), HOH_NOIX_LANES (compact tables, up to 64 chains per workgroup),
  * HOH_NOIX_MULTI (full tables, 12 chains per CU) or HOH_NOIX_WAVE (one wave per stream).  Every
- * choice gives the same bytes; the library reads no environment variables for it. */
+ * choice gives the same bytes; the library reads no environment variables for it.  hoh_index_build
+ * walks the same chains and follows the option (lanes or multi; HOH_NOIX_WAVE reads as adaptive). */
 #define HOH_OPT_NOIX_DECODER 1
 #define HOH_NOIX_ADAPTIVE (-1)
 #define HOH_NOIX_LANES 0
@@ -127,6 +128,57 @@ size_t hoh_index_bytes(const hoh_index* idx);
 int hoh_encode_image_ix(hoh_ctx* ctx, const uint8_t* d_rgb, int W, int H, int speed,
                         uint8_t* d_out, size_t cap, size_t* out_size, size_t* printed,
                         hoh_index* idx, void* stream);
+/* An EMPTY index (no streams: a fresh one, the one a -s1..-s4 encode leaves, a failed build or
+ * load) is accepted by every decode entry point as no index at all, whatever n and stride. */
+
+/* ---- side index beside the file: save, load, build, concatenate -------------------------
+ * hoh_index_serialize writes the index as a little-endian, position-independent blob (a sidecar
+ * file next to the .hoh); hoh_index_deserialize reads it back on any context or process.  The
+ * blob is canonical: indexes that describe the same streams of the same bytes serialize to the
+ * same bytes, whether an encode recorded them, hoh_index_build made them from the file or
+ * hoh_index_concat joined them.
+ *   header, 48 B:        'H','O','H','X'; u32 version = 1; u32 seg = 256 (symbols per checkpoint);
+ *                        u32 nstreams; u32 nimg; u32 0; u64 stride (0 when nimg == 1); u64 nck; u64 0
+ *   nstreams x 24 B:     u64 payload_off; u32 n; u32 mode; u32 words; u32 0
+ *   nck x 12 B:          u32 xl; u32 xh; u32 wi
+ * Stream s = tile * 7 + kind (kinds: three LZ streams, G, R, B planes, the indexed plane), tiles
+ * of a batch in image order.  mode: 0 empty or not in the file (the indexed plane of a sub-green
+ * tile, the planes of a palette tile), 1 rANS, 2 stored; a record whose mode is not 1 is zero
+ * elsewhere.  payload_off = byte of the first rANS payload word in the .hoh (in the batch buffer
+ * when nimg > 1: file i starts at i * stride); n = symbols; words = payload words.  A rANS stream
+ * owns ceil(n / seg) checkpoints, stored in stream order (its first one is the running sum of the
+ * streams before it; nck is the total): checkpoint k = the coder state (xh << 32 | xl) before
+ * symbol k * seg and wi = the index, inside the stream's own payload, of the next word the decoder
+ * reads.  The blob's length is exactly 48 + 24 nstreams + 12 nck; an empty index is its header.
+ * `stream` orders the calls behind the work that recorded the index (an encode enqueued on it);
+ * NULL waits for the whole device instead.  All three calls return with their work finished. */
+size_t hoh_index_serialized_size(const hoh_index* idx);    /* 0 on failure; waits for the device
+                                                              when an encode recorded idx         */
+/* HOH_E_CAP (with *written = the size needed) when cap is too small. */
+int hoh_index_serialize(const hoh_index* idx, uint8_t* out, size_t cap, size_t* written, void* stream);
+/* The blob is untrusted: it is validated on the host before any device call -- magic, version,
+ * seg, the reserved fields, nstreams a multiple of 7 and of nimg >= 1, stride == 0 exactly when
+ * nimg == 1, modes, zero non-rANS records, sum of ceil(n / seg) == nck, exact length (computed
+ * without overflow).  Any violation: HOH_E_CORRUPT and idx empty.  A well-formed blob with wrong
+ * VALUES (of another file, or edited) is safe to decode with: a stream's record is used only when
+ * its payload_off, n and words equal what the decoder parsed from the file, every payload read is
+ * bounded by the file size, and a wrong state fails the decode (HOH_E_CORRUPT) or, where no
+ * checkpoint matches, leaves the stream to the serial decoder. */
+int hoh_index_deserialize(hoh_index* idx, const uint8_t* blob, size_t size, void* stream);
+/* An index for any .hoh, from its bytes alone (d_hoh: `size` bytes on the device; synchronous;
+ * W, H optional outputs): the decoder's header / tile / stream parse, then one pass over every
+ * rANS chain that stores no symbols, only the checkpoints.  The result serializes to the bytes of
+ * the index hoh_encode_image_ix records for the same file.  HOH_E_UNSUPPORTED (idx empty) for a
+ * file the indexed decoder does not cover in full: general tiles (RGB mode, a fourth LZ stream,
+ * predictor maps -- every HOH_OPT_DECODABLE -s>=1 file), palette / grey / bitimage tiles, a stream
+ * with range > 512 or prob_bits > 15, untiled files.  HOH_E_CORRUPT (idx empty) for a chain that
+ * runs out of payload or does not end in the initial state, and for any framing error. */
+int hoh_index_build(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, hoh_index* idx, int* W, int* H, void* stream);
+/* dst = the index of n files laid out at i * stride, as hoh_decode_images_async reads them, from
+ * their n single-image indexes (equal stream counts, else HOH_E_ARG; dst must not be a source).
+ * Serializes to the bytes of the index hoh_encode_images_async(n, .., stride, idx) records for the
+ * same files.  n == 1 copies (stride ignored). */
+int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream);
 
 /* Replaces dhoh.cpp:297-396 (with the decoder defects of SURVEY Q1, Q9-Q12 fixed).  d_hoh holds
  * `size` bytes of a .hoh file; writes W*H*3 RGB bytes to d_rgb.  Every decode entry point reads,
@@ -170,7 +222,7 @@ int hoh_decode_image_async(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, int 
  * stride, HOH_E_UNREPRODUCIBLE, ...) mark only its slot; a failure of the job marks every slot.
  * Files are byte-identical to the single-image calls'.  One side index serves the whole batch
  * (payload positions are absolute in the batch buffer), so a decode with it needs the same n and
- * stride (else HOH_E_ARG).  The batch runs as one job when its tiles stack -- H a multiple of 256,
+ * stride (else HOH_E_ARG; an empty index passes with any).  The batch runs as one job when its tiles stack -- H a multiple of 256,
  * so the n images are the 256-row tile grid of one n*H image; at -s1..-s4 (whose workspace is ~8 MB
  * per tile) as stacks of up to 1024 tiles (one 8192^2 image, or 64 of 1024^2) one after another,
  * and no side index (idx, if given, is emptied as in the single-image calls); otherwise tiled

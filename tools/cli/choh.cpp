@@ -7,6 +7,8 @@
 // (hoh_mgpu_encode_image: a band of tile rows per device, one RCCL gather); same bytes.
 // `--decodable` (anywhere on the line) sets HOH_OPT_DECODABLE: the file differs from the
 // reference's at -s1..-s4 and can be read back by dhoh (one GPU only).
+// `--index out.hix` (after the reference's arguments) also writes the encode's side index as a
+// sidecar blob (hoh_index_serialize; the empty index at -s1..-s4) for `dhoh --index`; one GPU only.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -29,15 +31,21 @@ static bool read_file(const char* path, std::vector<uint8_t>& b) {
 
 int main(int argc, char** argv) {
   bool decodable = false;
+  const char* hix = nullptr;
   {
     int w = 1;
     for (int i = 1; i < argc; i++) {
       if (!std::strcmp(argv[i], "--decodable")) decodable = true;
+      else if (!std::strcmp(argv[i], "--index") && i + 1 < argc) hix = argv[++i];
       else argv[w++] = argv[i];
     }
     argc = w;
   }
   const std::vector<int> devices = take_devices(argc, argv);
+  if (hix && devices.size() > 1) {
+    std::printf("--index encodes on one GPU\n");
+    return 1;
+  }
   if (decodable && devices.size() > 1) {
     std::printf("--decodable encodes on one GPU\n");
     return 1;
@@ -76,9 +84,21 @@ int main(int argc, char** argv) {
   if (hipMalloc(&d_out, cap) != hipSuccess) return HOH_E_HIP;
   if (!mg && hipMemcpy(d_in, in.data(), raw, hipMemcpyHostToDevice) != hipSuccess) return HOH_E_HIP;
   size_t n = 0, printed = 0;
+  hoh_index* ix = nullptr;
+  if (hix && (r = hoh_index_create(&ix)) != HOH_OK) { std::fprintf(stderr, "choh: %s\n", hoh_strerror(r)); return r; }
   r = mg ? hoh_mgpu_encode_image(mg, in.data(), W, H, speed, d_out, cap, &n, &printed)
-         : hoh_encode_image(ctx, d_in, W, H, speed, d_out, cap, &n, &printed, nullptr);
+         : hoh_encode_image_ix(ctx, d_in, W, H, speed, d_out, cap, &n, &printed, ix, nullptr);
   if (r != HOH_OK) { std::fprintf(stderr, "choh: %s\n", hoh_strerror(r)); return r; }
+  if (ix) {
+    std::vector<uint8_t> blob(hoh_index_serialized_size(ix));
+    size_t bn = 0;
+    r = hoh_index_serialize(ix, blob.data(), blob.size(), &bn, hoh_ctx_stream(ctx));
+    if (r != HOH_OK) { std::fprintf(stderr, "choh: %s\n", hoh_strerror(r)); return r; }
+    FILE* xf = std::fopen(hix, "wb");
+    if (!xf || std::fwrite(blob.data(), 1, bn, xf) != bn) { std::printf("could not write %s\n", hix); return 3; }
+    std::fclose(xf);
+    hoh_index_destroy(ix);
+  }
   std::vector<uint8_t> out(n);
   if (n && hipMemcpy(out.data(), d_out, n, hipMemcpyDeviceToHost) != hipSuccess) return HOH_E_HIP;
   std::printf("%d\n", (int)printed);

@@ -3,6 +3,10 @@
 // interleaved RGB bytes.  Return codes: 3/4 not a .hoh, 5 unknown pixel format, and the
 // library's status code for anything it cannot decode.  `--gpus N` / `--devices a,b,..`
 // (tools/cli/gpus.h) decode over several GPUs in this process (hoh_mgpu_decode_image).
+// After the reference's arguments (one GPU only): `--index in.hix` decodes with the side index in
+// that sidecar (hoh_index_deserialize; choh --index or dhoh --write-index wrote it);
+// `--write-index out.hix` builds the index from the file (hoh_index_build), writes it and decodes
+// with it -- for a file the builder does not cover it writes the empty index and decodes without.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -12,7 +16,21 @@
 #include "gpus.h"
 
 int main(int argc, char** argv) {
+  const char *hix_in = nullptr, *hix_out = nullptr;
+  {
+    int w = 1;
+    for (int i = 1; i < argc; i++) {
+      if (!std::strcmp(argv[i], "--index") && i + 1 < argc) hix_in = argv[++i];
+      else if (!std::strcmp(argv[i], "--write-index") && i + 1 < argc) hix_out = argv[++i];
+      else argv[w++] = argv[i];
+    }
+    argc = w;
+  }
   const std::vector<int> devices = take_devices(argc, argv);
+  if ((hix_in || hix_out) && devices.size() > 1) {
+    std::printf("--index / --write-index decode on one GPU\n");
+    return 1;
+  }
   if (argc == 2 && (!std::strcmp(argv[1], "--help") || !std::strcmp(argv[1], "-h"))) {
     std::printf("usage: dhoh infile.hoh outfile.rgb\n");
     return 0;
@@ -54,7 +72,38 @@ int main(int argc, char** argv) {
   if (mg) {
     r = hoh_mgpu_decode_image(mg, d_in, in.size(), out.data(), raw, &W, &H);
   } else {
-    r = hoh_decode_image(ctx, d_in, in.size(), d_rgb, raw, &W, &H, nullptr);
+    hoh_index* ix = nullptr;
+    if (hix_in || hix_out) {
+      if ((r = hoh_index_create(&ix)) != HOH_OK) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
+    }
+    if (hix_in) {
+      std::vector<uint8_t> blob;
+      FILE* xf = std::fopen(hix_in, "rb");
+      if (!xf) { std::printf("could not read %s\n", hix_in); return 3; }
+      std::fseek(xf, 0, SEEK_END);
+      const long bn = std::ftell(xf);
+      std::fseek(xf, 0, SEEK_SET);
+      blob.resize(bn > 0 ? (size_t)bn : 0);
+      const bool got = blob.empty() || std::fread(blob.data(), 1, blob.size(), xf) == blob.size();
+      std::fclose(xf);
+      if (!got) { std::printf("could not read %s\n", hix_in); return 3; }
+      r = hoh_index_deserialize(ix, blob.data(), blob.size(), nullptr);
+      if (r != HOH_OK) { std::fprintf(stderr, "dhoh: %s: %s\n", hix_in, hoh_strerror(r)); return r; }
+    }
+    if (hix_out) {
+      int bw = 0, bh = 0;
+      r = hoh_index_build(ctx, d_in, in.size(), ix, &bw, &bh, nullptr);
+      if (r != HOH_OK && r != HOH_E_UNSUPPORTED) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
+      std::vector<uint8_t> blob(hoh_index_serialized_size(ix));   // the empty index when unsupported
+      size_t bn = 0;
+      r = hoh_index_serialize(ix, blob.data(), blob.size(), &bn, hoh_ctx_stream(ctx));
+      if (r != HOH_OK) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
+      FILE* xf = std::fopen(hix_out, "wb");
+      if (!xf || std::fwrite(blob.data(), 1, bn, xf) != bn) { std::printf("could not write %s\n", hix_out); return 3; }
+      std::fclose(xf);
+    }
+    r = hoh_decode_image_ix(ctx, d_in, in.size(), d_rgb, raw, &W, &H, ix, nullptr);
+    if (ix) hoh_index_destroy(ix);
     if (r == HOH_OK && hipMemcpy(out.data(), d_rgb, raw, hipMemcpyDeviceToHost) != hipSuccess) r = HOH_E_HIP;
   }
   if (r != HOH_OK) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
