@@ -51,12 +51,44 @@ struct GenTile {
   GenLayer L[3];
 };
 
+#define HOH_DEC_NBUF 20      // slots 16..18: a region decode's staging surface, whole-file tile table and gid
 struct DecWork {
-  void* bufs[16] = {nullptr};
-  size_t sizes[16] = {0};
+  void* bufs[HOH_DEC_NBUF] = {nullptr};
+  size_t sizes[HOH_DEC_NBUF] = {0};
   hipEvent_t noix_ev = nullptr;   // recorded after this context's last no-index chain kernel
   int noix_dev = -1;              // device it is registered on (k_decode.hip, noix_busy)
   int64_t noix_t = 0;             // host time (steady clock, us) of its last no-index decode
+};
+
+// Region decode (hoh_decode_region*, k_region.hip): the w x h window at (xy[2i], xy[2i+1]) of file
+// i of n files of one W x H shape.  Passed to k_dregion / k_dcrop by value (the windows are host
+// data of the call; 256 pairs are 2 KB of kernel arguments), so no host buffer outlives the call.
+#define HOH_REGION_MAX_BATCH 256
+struct RegionArgs {
+  int32_t n;                        // files
+  int32_t W, H, xt, yt, tw, th;     // the files' geometry (hoh_tiling)
+  int32_t w, h;                     // the window's size
+  int32_t file_tiles;               // xt * yt
+  int32_t sw, sh;                   // staging slab of one file: pitch in pixels (a multiple of 16), rows
+  int32_t ntiles;                   // covered tiles of all files (the job's tile count)
+  int32_t xy[2 * HOH_REGION_MAX_BATCH];
+};
+// tile rectangle covering pixels [x, x+w) x [y, y+h): tile columns / rows start at multiples of
+// tw / th (the last ones may be narrower), so the cover is a pair of divisions
+__host__ __device__ inline void region_cover_hd(int tw, int th, int x, int y, int w, int h, int* tx0, int* ty0,
+                                                int* ntx, int* nty) {
+  *tx0 = x / tw; *ty0 = y / th;
+  *ntx = (x + w - 1) / tw - *tx0 + 1;
+  *nty = (y + h - 1) / th - *ty0 + 1;
+}
+void launch_dregion(const RegionArgs& a, const DecTile* table, DecTile* tiles, uint32_t* gid, uint32_t* gerr,
+                    hipStream_t s);
+void launch_dcrop(const RegionArgs& a, const uint8_t* stage, uint8_t* dst, size_t pitch, const uint32_t* gerr,
+                  hipStream_t s);
+struct RegionJob {                  // what decode_run needs beside the DecJob of a region decode
+  RegionArgs a;
+  uint8_t* dst;                     // the caller's buffer and pitch (bytes)
+  size_t pitch;
 };
 
 void dec_free(DecWork& w);

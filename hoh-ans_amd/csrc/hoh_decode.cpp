@@ -20,6 +20,14 @@ int decode_tiles_async_impl(hoh_ctx* c, const uint8_t* d_blob, size_t size, int 
 int decode_tiles_images_async_impl(hoh_ctx* c, int n, const uint8_t* d_blob, size_t stride, int W, int H, int t0,
                                    int ntiles, const uint32_t* d_sizes, uint8_t* d_rgb, const hoh_index* idx,
                                    uint64_t* d_status, hipStream_t s);
+int decode_region_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int x, int y, int w, int h, uint8_t* d_rgb,
+                       size_t pitch, size_t cap, int* Wp, int* Hp, const hoh_index* idx, hipStream_t s);
+int decode_region_async_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int W, int H, int x, int y, int w, int h,
+                             uint8_t* d_rgb, size_t pitch, size_t cap, const hoh_index* idx, uint64_t* d_status,
+                             hipStream_t s);
+int decode_regions_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, int W, int H, const int32_t* h_xy,
+                              int w, int h, uint8_t* d_rgb, size_t pitch, const hoh_index* idx, uint64_t* d_status,
+                              hipStream_t s);
 int decode_stream_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, size_t* bp, uint16_t* d_out, size_t cap,
                        size_t* n, hipStream_t s);
 int encode_streams_impl(hoh_ctx* c, const uint16_t* d_syms, const uint64_t* off, const uint32_t* cnt, int nstreams,
@@ -105,6 +113,40 @@ int hoh_decode_tiles_images_async(hoh_ctx* c, int n, const uint8_t* d_blob, size
   (void)hipSetDevice(ctx_device(c));
   return decode_tiles_images_async_impl(c, n, d_blob, stride, W, H, t0, ntiles, d_tile_sizes, d_rgb, idx, d_status,
                                         ctx_stream(c, stream));
+}
+
+int hoh_region_cover(int W, int H, int x, int y, int w, int h, int* tx0, int* ty0, int* ntx, int* nty) {
+  if (!tx0 || !ty0 || !ntx || !nty) return HOH_E_ARG;
+  if (W <= 0 || H <= 0 || w <= 0 || h <= 0 || x < 0 || y < 0 || x > W - w || y > H - h) return HOH_E_ARG;
+  int xt, yt, tw, th;
+  if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) return HOH_E_UNSUPPORTED;
+  region_cover_hd(tw, th, x, y, w, h, tx0, ty0, ntx, nty);
+  return HOH_OK;
+}
+
+int hoh_decode_region(hoh_ctx* c, const uint8_t* d_hoh, size_t size, int x, int y, int w, int h, uint8_t* d_rgb,
+                      size_t pitch, size_t cap, int* W, int* H, const hoh_index* idx, void* stream) {
+  if (!c || !d_hoh || !d_rgb) return HOH_E_ARG;
+  (void)hipSetDevice(ctx_device(c));
+  return decode_region_impl(c, d_hoh, size, x, y, w, h, d_rgb, pitch, cap, W, H, idx, ctx_stream(c, stream));
+}
+
+int hoh_decode_region_async(hoh_ctx* c, const uint8_t* d_hoh, size_t size, int W, int H, int x, int y, int w, int h,
+                            uint8_t* d_rgb, size_t pitch, size_t cap, const hoh_index* idx, uint64_t* d_status,
+                            void* stream) {
+  if (!c || !d_hoh || !d_rgb || !d_status) return HOH_E_ARG;
+  (void)hipSetDevice(ctx_device(c));
+  return decode_region_async_impl(c, d_hoh, size, W, H, x, y, w, h, d_rgb, pitch, cap, idx, d_status,
+                                  ctx_stream(c, stream));
+}
+
+int hoh_decode_regions_async(hoh_ctx* c, int n, const uint8_t* d_hoh, size_t stride, int W, int H, const int32_t* h_xy,
+                             int w, int h, uint8_t* d_rgb, size_t pitch, const hoh_index* idx, uint64_t* d_status,
+                             void* stream) {
+  if (!c || !d_hoh || !d_rgb || !d_status || !h_xy || stride == 0) return HOH_E_ARG;
+  (void)hipSetDevice(ctx_device(c));
+  return decode_regions_async_impl(c, n, d_hoh, stride, W, H, h_xy, w, h, d_rgb, pitch, idx, d_status,
+                                   ctx_stream(c, stream));
 }
 
 int hoh_decode_image(hoh_ctx* c, const uint8_t* d_hoh, size_t size, uint8_t* d_rgb, size_t cap, int* W, int* H,

@@ -64,6 +64,9 @@ struct DecJob {
   uint64_t in_stride;           //   image their stack, file i at in + i * in_stride (nimg <= 1: one file)
   uint32_t exp;                 // measurement what-ifs (knob EXP, knob builds only; 0 in the product)
   GenTile* gen;                 // [tile] general tiles' layer headers (DecTile.gen, k_dgen)
+  int we;                       // width of the files' edge tile column (decode_run; a region job's W is its staging pitch)
+  const uint32_t* gid;          // region job: [tile] its number in the side index's numbering, file * file_tiles
+  int file_tiles;               //   + tile of the file; file_tiles = tiles of one whole file (null / 0 otherwise)
 };
 
 // general tiles' extra streams: slot k (0: the fourth LZ stream, 1..3: the layers' maps) of tile t,
@@ -347,14 +350,17 @@ __device__ bool parse_stream(const DecJob& j, uint64_t& p, int sid, uint64_t out
   return true;
 }
 
-__global__ __launch_bounds__(64) void k_dparse(DecJob job) {
+// REGION: a region job (k_dparse_gid), whose tile t belongs to the file gid names; the other jobs'
+// k_dparse compiles as it did before the region calls existed
+template <bool REGION>
+__device__ __forceinline__ void dparse_tile(const DecJob& job) {
   if (dec_abort(job)) return;
   const int t = blockIdx.x, lane = threadIdx.x;
   // a batch: every bound check of this tile's framing and streams stops at its own file's end
   // (file i is [i * in_stride, (i + 1) * in_stride)), so a truncated file reads as corrupt instead
   // of running on into the next file's bytes
   DecJob j = job;
-  if (j.nimg > 1) j.size = min(job.size, (uint64_t)(t / j.img_tiles + 1) * j.in_stride);
+  if (j.nimg > 1) j.size = min(job.size, (uint64_t)((REGION ? (int)j.gid[t] / j.file_tiles : t / j.img_tiles) + 1) * j.in_stride);
   DecTile ti = j.tiles[t];
   uint64_t p = ti.off;
   bool ok = p + 4 <= j.size;
@@ -442,6 +448,9 @@ __global__ __launch_bounds__(64) void k_dparse(DecJob job) {
   }
 }
 
+__global__ __launch_bounds__(64) void k_dparse(DecJob job) { dparse_tile<false>(job); }
+__global__ __launch_bounds__(64) void k_dparse_gid(DecJob job) { dparse_tile<true>(job); }
+
 // match the decoder's streams to the side index by payload position
 __global__ void k_dmatch(DecJob j, int nstreams) {
   if (dec_abort(j)) return;
@@ -451,6 +460,21 @@ __global__ void k_dmatch(DecJob j, int nstreams) {
   const IndexStream x = j.ix[s];
   if (d.mode == SM_RANS && x.mode == SM_RANS && x.payload_off == d.payload_off && x.n == d.n && x.words == d.words) {
     j.streams[s].ix = s;
+  }
+}
+
+// a region job: local stream lt * 7 + k is stream gid[lt] * 7 + k of the whole file's (batch's) index
+__global__ void k_dmatch_gid(DecJob j, int nstreams) {
+  if (dec_abort(j)) return;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nstreams) return;
+  const int lt = s / SK_PER_TILE;
+  const int64_t g = (int64_t)j.gid[lt] * SK_PER_TILE + (s - lt * SK_PER_TILE);
+  if (g >= j.nix) return;
+  DecStream d = j.streams[s];
+  const IndexStream x = j.ix[g];
+  if (d.mode == SM_RANS && x.mode == SM_RANS && x.payload_off == d.payload_off && x.n == d.n && x.words == d.words) {
+    j.streams[s].ix = (int32_t)g;
   }
 }
 
@@ -2921,7 +2945,8 @@ struct AsyncDec {              // enqueue-only decode: expected header bytes and
   uint64_t* status;
   uint64_t bytes;               // the status size word on success
 };
-static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s, const AsyncDec* as = nullptr);
+static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s, const AsyncDec* as = nullptr,
+                      const RegionJob* rg = nullptr);
 void launch_status_dec(const uint32_t* gerr, uint64_t bytes, uint64_t* out, hipStream_t s, int n = 1);
 
 int decode_image_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, uint8_t* d_rgb, size_t cap, int* Wp, int* Hp,
@@ -3143,6 +3168,121 @@ int decode_tiles_images_async_impl(hoh_ctx* c, int n, const uint8_t* d_blob, siz
   return decode_run(c, j, idx, s, &as);
 }
 
+// Region decode (hoh_decode_region*): the w x h window at (h_xy[2i], h_xy[2i+1]) of file i of n W x H
+// files (file i at d_in + i * stride; n == 1: one file of `stride` bytes).  The job's tiles are the
+// windows' covers only (region_cover_hd), decoded into a staging surface of one slab per file,
+// sized for the largest cover a w x h window can have, so a repeat call of the shape allocates
+// nothing wherever its windows lie; k_dcrop then copies each window to d_rgb + i * h * pitch.
+// d_status null: synchronous (the caller has checked the header on the host); otherwise enqueue-only,
+// the header checked on the device, {status, w * h * 3} per file in d_status.
+static int region_run(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, int W, int H, const int32_t* h_xy, int w,
+                      int h, uint8_t* d_rgb, size_t pitch, const hoh_index* idx, uint64_t* d_status, hipStream_t s) {
+  DecJob j;
+  memset(&j, 0, sizeof(j));
+  j.xt = W / 256; j.yt = H / 256;
+  j.tw = (W + j.xt - 1) / j.xt; j.th = (H + j.yt - 1) / j.yt;
+  RegionJob rg;
+  RegionArgs& a = rg.a;
+  memset(&a, 0, sizeof(a));
+  a.n = n;
+  a.W = W; a.H = H; a.xt = j.xt; a.yt = j.yt; a.tw = j.tw; a.th = j.th;
+  a.w = w; a.h = h;
+  a.file_tiles = j.xt * j.yt;
+  // a window of w pixels meets at most (w - 2) / tw + 2 tile columns (the seams lie at multiples of tw)
+  const int mcols = std::min(j.xt, (w + j.tw - 2) / j.tw + 1), mrows = std::min(j.yt, (h + j.th - 2) / j.th + 1);
+  a.sw = (mcols * j.tw + 15) & ~15;
+  a.sh = mrows * j.th;
+  int64_t nt = 0;
+  for (int i = 0; i < n; i++) {
+    int tx0, ty0, ntx, nty;
+    a.xy[2 * i] = h_xy[2 * i]; a.xy[2 * i + 1] = h_xy[2 * i + 1];
+    region_cover_hd(j.tw, j.th, a.xy[2 * i], a.xy[2 * i + 1], w, h, &tx0, &ty0, &ntx, &nty);
+    nt += (int64_t)ntx * nty;
+  }
+  if (nt > (1 << 24) || (int64_t)a.sh * n > (1ll << 30) || (int64_t)a.file_tiles * n > (1 << 24)) return 1;
+  a.ntiles = (int)nt;
+  rg.dst = d_rgb;
+  rg.pitch = pitch;
+  uint8_t hb[16];
+  int p = 0;
+  hb[p++] = 153; hb[p++] = 72; hb[p++] = 79; hb[p++] = 72; hb[p++] = 2; hb[p++] = 8;   // choh.cpp:437-446
+  for (uint32_t v : {(uint32_t)W - 1, (uint32_t)H - 1}) p = (int)hoh_write_varint(hb, (uint32_t)p, v);
+  hb[p++] = (uint8_t)(j.xt - 1);
+  hb[p++] = (uint8_t)(j.yt - 1);
+  AsyncDec as;
+  as.hdr[0] = as.hdr[1] = 0;
+  for (int i = 0; i < p; i++) as.hdr[i / 8] |= (uint64_t)hb[i] << (8 * (i % 8));
+  as.hl = p;
+  as.status = d_status;
+  as.bytes = (uint64_t)w * h * 3;
+  j.W = a.sw; j.H = a.sh * n;                     // the staging surface (decode_run points j.rgb at it)
+  j.we = W - (j.xt - 1) * j.tw;
+  j.prefix = (uint64_t)p;
+  j.ntiles = a.ntiles;
+  j.nimg = n > 1 ? n : 0;
+  j.img_tiles = a.file_tiles;
+  j.in_stride = n > 1 ? stride : 0;
+  j.in = d_in;
+  j.size = (uint64_t)n * stride;
+  return decode_run(c, j, idx, s, d_status ? &as : nullptr, &rg);
+}
+
+// HOH_E_ARG / HOH_E_UNSUPPORTED / HOH_E_CAP of the region calls, before any device work
+static int region_check(int W, int H, int x, int y, int w, int h, size_t pitch, size_t cap, bool has_cap) {
+  if (W <= 0 || H <= 0 || w <= 0 || h <= 0 || x < 0 || y < 0 || x > W - w || y > H - h) return 1;
+  if (pitch < (size_t)w * 3) return 1;
+  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;   // header-only files (Q13) have no tiles
+  if (has_cap && cap < (size_t)(h - 1) * pitch + (size_t)w * 3) return 2;
+  return 0;
+}
+
+int decode_region_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int x, int y, int w, int h, uint8_t* d_rgb,
+                       size_t pitch, size_t cap, int* Wp, int* Hp, const hoh_index* idx, hipStream_t s) {
+  // header (host copy of the first bytes, as decode_image_impl)
+  uint8_t hb[16] = {0};
+  const size_t hn = size < 16 ? size : 16;
+  if (hipMemcpyAsync(hb, d_in, hn, hipMemcpyDeviceToHost, s) != hipSuccess) return 3;
+  if (hipStreamSynchronize(s) != hipSuccess) return 3;
+  if (hn < 8 || hb[0] != 153 || hb[1] != 72 || hb[2] != 79 || hb[3] != 72) return 7;
+  if (hb[4] != 2 || hb[5] != 8) return 6;
+  uint64_t p = 6, wv = 0, hv = 0;
+  for (uint64_t* v : {&wv, &hv}) {                           // varint.hpp:6-27 (at most 3 bytes each)
+    const uint64_t b0 = hb[p++];
+    if (!(b0 & 0x80)) { *v = b0; continue; }
+    const uint64_t b1 = hb[p++];
+    if (!(b1 & 0x80)) { *v = ((b0 & 0x7f) << 7) + b1; continue; }
+    *v = ((b0 & 0x7f) << 14) + ((b1 & 0x7f) << 7) + hb[p++];
+  }
+  const int W = (int)wv + 1, H = (int)hv + 1;
+  if (Wp) *Wp = W;
+  if (Hp) *Hp = H;
+  const int r = region_check(W, H, x, y, w, h, pitch, cap, true);
+  if (r) return r;
+  if (p + 2 > size || hb[p] != (uint8_t)(W / 256 - 1) || hb[p + 1] != (uint8_t)(H / 256 - 1)) return 7;
+  const int32_t xy[2] = {x, y};
+  return region_run(c, 1, d_in, size, W, H, xy, w, h, d_rgb, pitch, idx, nullptr, s);
+}
+
+int decode_region_async_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int W, int H, int x, int y, int w, int h,
+                             uint8_t* d_rgb, size_t pitch, size_t cap, const hoh_index* idx, uint64_t* d_status,
+                             hipStream_t s) {
+  const int r = region_check(W, H, x, y, w, h, pitch, cap, true);
+  if (r) return r;
+  const int32_t xy[2] = {x, y};
+  return region_run(c, 1, d_in, size, W, H, xy, w, h, d_rgb, pitch, idx, d_status, s);
+}
+
+int decode_regions_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, int W, int H, const int32_t* h_xy,
+                              int w, int h, uint8_t* d_rgb, size_t pitch, const hoh_index* idx, uint64_t* d_status,
+                              hipStream_t s) {
+  if (n <= 0 || n > HOH_REGION_MAX_BATCH) return 1;
+  for (int i = 0; i < n; i++) {
+    const int r = region_check(W, H, h_xy[2 * i], h_xy[2 * i + 1], w, h, pitch, 0, false);
+    if (r) return r;
+  }
+  return region_run(c, n, d_in, stride, W, H, h_xy, w, h, d_rgb, pitch, idx, d_status, s);
+}
+
 // copies reading the row above that make an LZ tile a chain tile (knobs LZ_XROW, LZ_XROW_BATCH).
 // A batch decodes many images' LZ tiles at once, and there the raster chains (less work per tile
 // than the dynamic wavefront) pay from 2 such copies on: natural 8192^2 -s0 pipeline 50.1 -> 53.5
@@ -3210,8 +3350,10 @@ static uint32_t dl_budget() {
 }
 static int dl_wg_per_cu() { return std::max(1, HOH_KNOB(DL_WG, 3)); }
 
-static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s, const AsyncDec* as) {
+static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s, const AsyncDec* as,
+                      const RegionJob* rg) {
   j.exp = (uint32_t)HOH_KNOB(EXP, 0);
+  if (!rg) j.we = j.W - (j.xt - 1) * j.tw;      // the edge column's width (a region job brings its files')
   j.npix_cap = (uint32_t)(((size_t)j.tw * j.th + 63) / 64 * 64);
   j.lz_cap = (uint32_t)((j.npix_cap / 4 + j.npix_cap / 255 + 16 + 7) / 8 * 8);
   {
@@ -3244,8 +3386,21 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
 #else
   if ((e = dbuf(w, 15, (size_t)j.ntiles * j.th * ((j.tw + 15) & ~15) + 16, &q))) return e; j.bmap = (uint8_t*)q;
 #endif
+  // a region job: the whole files' tile table (k_dtable's scratch), the covered tiles' numbers and
+  // the staging surface the writers fill (a slab of sh rows per file, + 16 B the crop may read past)
+  DecTile* rtable = nullptr;
+  uint32_t* rgid = nullptr;
+  const int nfiles = j.nimg > 1 ? j.nimg : 1;
+  if (rg) {
+    const RegionArgs& a = rg->a;
+    if ((e = dbuf(w, 16, (size_t)a.sw * a.sh * nfiles * 3 + 16, &q))) return e; j.rgb = (uint8_t*)q;
+    if ((e = dbuf(w, 17, (size_t)a.file_tiles * nfiles * sizeof(DecTile), &q))) return e; rtable = (DecTile*)q;
+    if ((e = dbuf(w, 18, (size_t)j.ntiles * 4, &q))) return e; rgid = (uint32_t*)q;
+    j.gid = rgid;
+    j.file_tiles = a.file_tiles;
+  }
   j.lz_xrow = lz_xrow(j.nimg > 1);
-  if (index_nstreams(idx)) {                   // a batch's index serves that batch's layout only (an empty one: any)
+  if (index_nstreams(idx)) {                  // a batch's index serves that batch's layout only (an empty one: any)
     uint64_t st = 0;
     const int ni = index_batch(idx, &st);
     if (ni != (j.nimg > 1 ? j.nimg : 1) || (ni > 1 && st != j.in_stride)) return 1;
@@ -3253,18 +3408,34 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   j.ix = index_streams(idx);
   j.ck = index_ckpts(idx);
   j.nix = index_nstreams(idx);
-  const int indexed = j.ix && j.nix == S;
+  // the index is the whole file's (batch's): its stream count is 7 per tile of the files, not of the job
+  const int indexed = j.ix && j.nix == (rg ? rg->a.file_tiles * nfiles * SK_PER_TILE : S);
   if (hipMemsetAsync(j.gerr, 0, 64, s) != hipSuccess) return 3;
   if (hipMemsetAsync(j.streams, 0, (size_t)S2 * sizeof(DecStream), s) != hipSuccess) return 3;
   ctx_mark(c, s, "start", as == nullptr);
   const int nfile = j.nimg > 1 ? j.nimg : 1;
   if (as && as->hl) hipLaunchKernelGGL(k_dhdr, dim3(nfile), dim3(64), 0, s, j, as->hdr[0], as->hdr[1], as->hl);
-  hipLaunchKernelGGL(k_dtable, dim3(nfile), dim3(1024), 0, s, j);
+  if (rg) {
+    // every tile's offset from the whole table (a prefix sum: read whole, one workgroup per file),
+    // then the covered tiles' DecTile records and index numbers
+    DecJob jt = j;
+    jt.tiles = rtable;
+    jt.ntiles = rg->a.file_tiles * nfiles;
+    jt.img_tiles = rg->a.file_tiles;
+    jt.W = rg->a.W; jt.H = rg->a.H * nfiles;
+    jt.gid = nullptr;
+    hipLaunchKernelGGL(k_dtable, dim3(nfile), dim3(1024), 0, s, jt);
+    launch_dregion(rg->a, rtable, j.tiles, rgid, j.gerr, s);
+  } else {
+    hipLaunchKernelGGL(k_dtable, dim3(nfile), dim3(1024), 0, s, j);
+  }
   ctx_mark(c, s, "dtable", false);
-  hipLaunchKernelGGL(k_dparse, dim3(j.ntiles), dim3(64), 0, s, j);
+  if (rg) hipLaunchKernelGGL(k_dparse_gid, dim3(j.ntiles), dim3(64), 0, s, j);
+  else hipLaunchKernelGGL(k_dparse, dim3(j.ntiles), dim3(64), 0, s, j);
   ctx_mark(c, s, "dparse", false);
   if (indexed) {
-    hipLaunchKernelGGL(k_dmatch, dim3((S + 255) / 256), dim3(256), 0, s, j, S);
+    if (rg) hipLaunchKernelGGL(k_dmatch_gid, dim3((S + 255) / 256), dim3(256), 0, s, j, S);
+    else hipLaunchKernelGGL(k_dmatch, dim3((S + 255) / 256), dim3(256), 0, s, j, S);
     hipLaunchKernelGGL(k_drans, dim3(S), dim3(DR_T), DR_SMEM, s, j, S);
   } else if (ctx_noix(c) == HOH_NOIX_WAVE) {                  // the one-wave-per-stream decoder alone
     hipLaunchKernelGGL(k_drans_wave, dim3(S), dim3(64), DL_SMEM, s, j, S, 0);
@@ -3316,7 +3487,7 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   const int gsmall = std::min(j.ntiles, 256);
   hipLaunchKernelGGL(k_dbackmap, dim3(gsmall), dim3(256), 0, s, j);
   {
-    const int we = j.W - (j.xt - 1) * j.tw;
+    const int we = j.we;
     hipLaunchKernelGGL(k_dexpand, dim3(j.ntiles), dim3(256), 0, s, j, j.tw % 16 == 0 ? 1 : 0, we % 16 == 0 ? 1 : 0);
   }
   hipLaunchKernelGGL(k_dunpred_fast, dim3(j.ntiles), dim3(64), (size_t)64 * ORING_PITCH + 6 * LAST_N(j.tw), s, j);
@@ -3330,7 +3501,7 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     const int br_many = (int)std::min<size_t>(32, lds / rowb - 2);
     j.lzband = br_few;
     // + the chain tiles' workgroups (ring R >= 2w: row 0 reads T / TL from the initial half values)
-    const int we = j.W - (j.xt - 1) * j.tw;                             // the edge column's width
+    const int we = j.we;                                                // the edge column's width
     const int ga = (j.ntiles + CH_T - 1) / CH_T, gc = ga * (we != j.tw ? 2 : 1);
     const bool r512 = 2 * j.tw <= 512;
     const size_t cl = r512 ? ch_smem(512) : ch_smem(1024);
@@ -3351,6 +3522,10 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   ctx_mark(c, s, "dunpred", false);
   hipLaunchKernelGGL(k_dgen, dim3(3 * j.ntiles), dim3(64), dgen_smem(j.tw), s, j);   // general tiles
   ctx_mark(c, s, "dgen", false);
+  if (rg) {                                                            // the windows, out of the staging surface
+    launch_dcrop(rg->a, j.rgb, rg->dst, rg->pitch, j.gerr, s);
+    ctx_mark(c, s, "dcrop", false);
+  }
   if (hipGetLastError() != hipSuccess) return 3;
   if (as) {
     launch_status_dec(j.gerr, as->bytes, as->status, s, j.nimg > 1 ? j.nimg : 1);

@@ -96,6 +96,12 @@ def lib():
             ("hoh_decode_image_async", [vp, vp, sz, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
             ("hoh_encode_images_async", [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
             ("hoh_decode_images_async", [vp, C.c_int, vp, sz, C.c_int, C.c_int, vp, vp, vp, vp]),
+            ("hoh_region_cover", [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
+            ("hoh_decode_region", [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, sz, ip, ip, vp, vp]),
+            ("hoh_decode_region_async", [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, sz,
+                                         vp, vp, vp]),
+            ("hoh_decode_regions_async", [vp, C.c_int, vp, sz, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                          C.c_int, vp, sz, vp, vp, vp]),
             ("hoh_encode_tiles_async", [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, vp,
                                         vp]),
             ("hoh_decode_tiles_async", [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
@@ -392,6 +398,84 @@ def decode_images_async(hoh_dev, n, stride, W, H, out_dev, status_dev, ctx=None,
                                       _stream_ptr(torch, ctx))
     check(r, "hoh_decode_images_async")
     _after_call(torch, ctx)
+
+
+def region_cover(W, H, x, y, w, h):
+    """hoh_region_cover: (tx0, ty0, ntx, nty), the tile rectangle that holds pixels [x, x+w) x
+    [y, y+h) of a W x H image.  Host only."""
+    v = [C.c_int() for _ in range(4)]
+    check(lib().hoh_region_cover(W, H, x, y, w, h, *[C.byref(i) for i in v]), "hoh_region_cover")
+    return tuple(i.value for i in v)
+
+
+def _region_view(torch, out_dev, w, h, pitch):
+    """The (h, w, 3) window inside out_dev (rows pitch bytes apart); the flat buffer itself when
+    the pitch is no whole number of pixels (no uint8 (h, w, 3) stride expresses it)."""
+    if pitch % 3:
+        return out_dev
+    return torch.as_strided(out_dev, (h, w, 3), (pitch, 3, 1))
+
+
+def _region_out(torch, out_dev, w, h, pitch, n, device):
+    pitch = w * 3 if pitch is None else pitch
+    if out_dev is None:
+        out_dev = torch.empty(max((n * h - 1) * pitch + w * 3, 0), dtype=torch.uint8, device=device)
+    return out_dev, pitch
+
+
+def decode_region(hoh_dev, size, x, y, w, h, out_dev=None, pitch=None, ctx=None, index=None):
+    """hoh_decode_region: the w x h window at (x, y) of the .hoh in hoh_dev (`size` bytes), decoding
+    only the tiles it touches.  Row r lands at out_dev + r*pitch (bytes; default w*3, out_dev a new
+    buffer when None).  Returns (tensor, W, H): tensor is the uint8 (h, w, 3) window, a strided view
+    into out_dev; when pitch % 3 != 0 no such view exists and it is the flat out_dev."""
+    import torch
+    ctx = ctx or default_ctx()
+    out_dev, pitch = _region_out(torch, out_dev, w, h, pitch, 1, hoh_dev.device)
+    W, H = C.c_int(), C.c_int()
+    r = lib().hoh_decode_region(ctx.h, vp(hoh_dev.data_ptr()), size, x, y, w, h, vp(out_dev.data_ptr()), pitch,
+                                out_dev.numel(), C.byref(W), C.byref(H), index.h if index is not None else None,
+                                _stream_ptr(torch, ctx))
+    _after_call(torch, ctx)
+    check(r, "hoh_decode_region")
+    return _region_view(torch, out_dev, w, h, pitch), W.value, H.value
+
+
+def decode_region_async(hoh_dev, size, W, H, x, y, w, h, out_dev, status_dev, pitch=None, ctx=None, index=None):
+    """Enqueue-only hoh_decode_region_async of a W x H .hoh on the current stream (no host wait);
+    status_dev receives {HOH status code, w*h*3}.  Returns the window as decode_region does."""
+    import torch
+    ctx = ctx or default_ctx()
+    out_dev, pitch = _region_out(torch, out_dev, w, h, pitch, 1, hoh_dev.device)
+    r = lib().hoh_decode_region_async(ctx.h, vp(hoh_dev.data_ptr()), size, W, H, x, y, w, h, vp(out_dev.data_ptr()),
+                                      pitch, out_dev.numel(), index.h if index is not None else None,
+                                      vp(status_dev.data_ptr()), _stream_ptr(torch, ctx))
+    _after_call(torch, ctx)
+    check(r, "hoh_decode_region_async")
+    return _region_view(torch, out_dev, w, h, pitch)
+
+
+def decode_regions_async(hoh_dev, n, stride, W, H, xy, w, h, out_dev, status_dev, pitch=None, ctx=None, index=None):
+    """Enqueue-only hoh_decode_regions_async: crop i = the w x h window at xy[i] = (x, y) of file i
+    (n files of one shape at hoh_dev + i*stride), rows pitch bytes apart, crop i at out_dev +
+    i*h*pitch; status_dev: int64 tensor of 2n.  Returns the (n, h, w, 3) view of out_dev (the flat
+    out_dev when pitch % 3 != 0)."""
+    import torch
+    ctx = ctx or default_ctx()
+    out_dev, pitch = _region_out(torch, out_dev, w, h, pitch, n, hoh_dev.device)
+    flat = [int(v) for p in xy for v in p]
+    if n > 0 and len(flat) != 2 * n:
+        raise HohError(1, "hoh_decode_regions_async: xy holds %d values for n = %d" % (len(flat), n))
+    assert hoh_dev.numel() >= n * stride and status_dev.numel() >= 2 * n
+    assert n <= 0 or h <= 0 or w <= 0 or pitch < w * 3 or out_dev.numel() >= (n * h - 1) * pitch + w * 3
+    h_xy = (C.c_int32 * max(len(flat), 1))(*flat)
+    r = lib().hoh_decode_regions_async(ctx.h, n, vp(hoh_dev.data_ptr()), stride, W, H, h_xy, w, h,
+                                       vp(out_dev.data_ptr()), pitch, index.h if index is not None else None,
+                                       vp(status_dev.data_ptr()), _stream_ptr(torch, ctx))
+    _after_call(torch, ctx)
+    check(r, "hoh_decode_regions_async")
+    if pitch % 3:
+        return out_dev
+    return torch.as_strided(out_dev, (n, h, w, 3), (h * pitch, pitch, 3, 1))
 
 
 def check_status(status, what):

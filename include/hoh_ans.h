@@ -237,6 +237,47 @@ int hoh_encode_images_async(hoh_ctx* ctx, int n, const uint8_t* d_rgb, int W, in
 int hoh_decode_images_async(hoh_ctx* ctx, int n, const uint8_t* d_hoh, size_t stride, int W, int H, uint8_t* d_rgb,
                             const hoh_index* idx, uint64_t* d_status, void* stream);
 
+/* ---- region decode: a crop of a .hoh by decoding only its tiles ----------------------------
+ * The tiles of a .hoh share no state, so a pixel window needs only the tiles it touches.  The
+ * calls below restore the w x h window at (x, y): h rows of w*3 RGB bytes, row r at
+ * d_rgb + r*pitch (pitch in bytes, >= w*3, any value -- no multiple of 3 or 4 is asked; cap >=
+ * (h-1)*pitch + w*3).  No other byte of the caller's buffer is written, and the bytes written
+ * equal the same window of what hoh_decode_image restores.  Only the tiles of hoh_region_cover are
+ * parsed, entropy-decoded and unpredicted; the tile table is read whole (offsets are prefix sums)
+ * and the bytes of other tiles are never read, so a defect in a tile outside the cover does not
+ * fail the call, while one inside it fails as in a full decode (HOH_E_CORRUPT /
+ * HOH_E_UNSUPPORTED).  Every file kind the full decoder reads is read here, with or without a side
+ * index and under every HOH_OPT_NOIX_DECODER choice.  idx is the index of the WHOLE file (batch:
+ * of the whole batch, same n and stride, else HOH_E_ARG) however it came to be -- recorded, built,
+ * loaded, concatenated; the covered tiles' streams use their checkpoints; an empty index is no
+ * index.  HOH_E_ARG: an empty rectangle, one not inside the image, pitch < w*3, n out of range;
+ * HOH_E_UNSUPPORTED: an untiled shape (header-only files); HOH_E_CAP: cap too small.
+ * The tiles are decoded into a staging surface in the context's workspace (sized for the largest
+ * cover a w x h window can have, so after the first call of a shape a repeat call allocates no
+ * device memory wherever its window lies) and the window is copied out from there. */
+#define HOH_REGION_MAX_BATCH 256
+/* host only: the tile rectangle that covers pixels [x, x+w) x [y, y+h) of a W x H image
+ * (tiling of hoh_tiling): first tile column / row and the counts.  HOH_E_ARG for an empty
+ * rectangle or one not inside the image, HOH_E_UNSUPPORTED for an untiled shape. */
+int hoh_region_cover(int W, int H, int x, int y, int w, int h, int* tx0, int* ty0, int* ntx, int* nty);
+/* synchronous; reads W, H from the file as hoh_decode_image does (optional outputs) */
+int hoh_decode_region(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, int x, int y, int w, int h,
+                      uint8_t* d_rgb, size_t pitch, size_t cap, int* W, int* H,
+                      const hoh_index* idx, void* stream);
+/* enqueue-only (no host synchronisation); the caller gives W, H, the header is checked on the
+ * device (a mismatch: HOH_E_CORRUPT in the status); d_status = {status, w*h*3} */
+int hoh_decode_region_async(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, int W, int H,
+                            int x, int y, int w, int h, uint8_t* d_rgb, size_t pitch, size_t cap,
+                            const hoh_index* idx, uint64_t* d_status, void* stream);
+/* enqueue-only batch, one job: crop i = the w x h window at (h_xy[2i], h_xy[2i+1]) of file i (n
+ * files of one shape at d_hoh + i*stride, as hoh_decode_images_async reads them; any tiled shape,
+ * stacking or not), written at d_rgb + i*h*pitch; d_status holds 2n u64.  h_xy (host) is read
+ * only during the call.  Every parse of file i stays inside [i*stride, (i+1)*stride); an error in
+ * any file marks every slot.  n <= HOH_REGION_MAX_BATCH. */
+int hoh_decode_regions_async(hoh_ctx* ctx, int n, const uint8_t* d_hoh, size_t stride, int W, int H,
+                             const int32_t* h_xy, int w, int h, uint8_t* d_rgb, size_t pitch,
+                             const hoh_index* idx, uint64_t* d_status, void* stream);
+
 /* Host-side header parse: W, H and tiling of a .hoh (dhoh.cpp:320-366). */
 int hoh_peek_header(const uint8_t* hoh, size_t size, int* W, int* H, int* x_tiles, int* y_tiles);
 

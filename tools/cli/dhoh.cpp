@@ -7,6 +7,9 @@
 // that sidecar (hoh_index_deserialize; choh --index or dhoh --write-index wrote it);
 // `--write-index out.hix` builds the index from the file (hoh_index_build), writes it and decodes
 // with it -- for a file the builder does not cover it writes the empty index and decodes without.
+// `--region x,y,w,h` (one GPU, with or without the index options) decodes only the tiles that
+// window touches (hoh_decode_region) and writes its w*h*3 bytes; a malformed region or one not
+// inside the image prints the usage line and returns 1.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -16,12 +19,14 @@
 #include "gpus.h"
 
 int main(int argc, char** argv) {
-  const char *hix_in = nullptr, *hix_out = nullptr;
+  const char *hix_in = nullptr, *hix_out = nullptr, *region = nullptr;
+  static const char* usage = "usage: dhoh infile.hoh outfile.rgb [--index in.hix] [--write-index out.hix] [--region x,y,w,h]\n";
   {
     int w = 1;
     for (int i = 1; i < argc; i++) {
       if (!std::strcmp(argv[i], "--index") && i + 1 < argc) hix_in = argv[++i];
       else if (!std::strcmp(argv[i], "--write-index") && i + 1 < argc) hix_out = argv[++i];
+      else if (!std::strcmp(argv[i], "--region") && i + 1 < argc) region = argv[++i];
       else argv[w++] = argv[i];
     }
     argc = w;
@@ -30,6 +35,18 @@ int main(int argc, char** argv) {
   if ((hix_in || hix_out) && devices.size() > 1) {
     std::printf("--index / --write-index decode on one GPU\n");
     return 1;
+  }
+  int rx = 0, ry = 0, rw = 0, rh = 0;
+  if (region) {
+    char extra = 0;
+    if (std::sscanf(region, "%d,%d,%d,%d%c", &rx, &ry, &rw, &rh, &extra) != 4 || rx < 0 || ry < 0 || rw <= 0 || rh <= 0) {
+      std::printf("bad region '%s'\n%s", region, usage);
+      return 1;
+    }
+    if (devices.size() > 1) {
+      std::printf("--region decodes on one GPU\n");
+      return 1;
+    }
   }
   if (argc == 2 && (!std::strcmp(argv[1], "--help") || !std::strcmp(argv[1], "-h"))) {
     std::printf("usage: dhoh infile.hoh outfile.rgb\n");
@@ -58,12 +75,16 @@ int main(int argc, char** argv) {
   int r = hoh_peek_header(in.data(), in.size(), &W, &H, &xt, &yt);
   if (r != HOH_OK) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
   std::printf("width: %d\nheight: %d\n", W, H);
+  if (region && (rx > W - rw || ry > H - rh)) {
+    std::printf("region '%s' is not inside the image\n%s", region, usage);
+    return 1;
+  }
   hoh_ctx* ctx = nullptr;
   const int dev0 = devices.empty() ? 0 : devices[0];   // --devices 3 / one entry: that GPU
   hoh_mgpu* mg = nullptr;
   r = devices.size() > 1 ? hoh_mgpu_create(&mg, (int)devices.size(), devices.data()) : hoh_ctx_create(&ctx, dev0);
   if (r != HOH_OK) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
-  const size_t raw = (size_t)W * H * 3;
+  const size_t raw = region ? (size_t)rw * rh * 3 : (size_t)W * H * 3;
   uint8_t *d_in = nullptr, *d_rgb = nullptr;
   (void)hipSetDevice(dev0);
   if (hipMalloc(&d_in, in.size()) != hipSuccess || (!mg && hipMalloc(&d_rgb, raw) != hipSuccess)) return HOH_E_HIP;
@@ -102,7 +123,8 @@ int main(int argc, char** argv) {
       if (!xf || std::fwrite(blob.data(), 1, bn, xf) != bn) { std::printf("could not write %s\n", hix_out); return 3; }
       std::fclose(xf);
     }
-    r = hoh_decode_image_ix(ctx, d_in, in.size(), d_rgb, raw, &W, &H, ix, nullptr);
+    if (region) r = hoh_decode_region(ctx, d_in, in.size(), rx, ry, rw, rh, d_rgb, (size_t)rw * 3, raw, &W, &H, ix, nullptr);
+    else r = hoh_decode_image_ix(ctx, d_in, in.size(), d_rgb, raw, &W, &H, ix, nullptr);
     if (ix) hoh_index_destroy(ix);
     if (r == HOH_OK && hipMemcpy(out.data(), d_rgb, raw, hipMemcpyDeviceToHost) != hipSuccess) r = HOH_E_HIP;
   }
