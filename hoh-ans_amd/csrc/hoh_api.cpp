@@ -86,6 +86,7 @@ struct hoh_ctx {
   int profiling = 0;
   int noix = HOH_NOIX_ADAPTIVE;  // HOH_OPT_NOIX_DECODER
   int decodable = 0;            // HOH_OPT_DECODABLE
+  int chain_tables = HOH_CHAIN_TABLES_AUTO;   // HOH_OPT_CHAIN_TABLES
   std::vector<std::string> knames;      // names of the marks recorded by the current call
   std::vector<hipEvent_t> kev;          // event pool, kev[0..nmark) recorded by the current call
   size_t nmark = 0;
@@ -224,6 +225,10 @@ int hoh_ctx_set_option(hoh_ctx* c, int option, int64_t value) {
     case HOH_OPT_DECODABLE:
       if (value != 0 && value != 1) return HOH_E_ARG;
       c->decodable = (int)value;
+      return HOH_OK;
+    case HOH_OPT_CHAIN_TABLES:
+      if (value < HOH_CHAIN_TABLES_AUTO || value > HOH_CHAIN_TABLES_GLOBAL) return HOH_E_ARG;
+      c->chain_tables = (int)value;
       return HOH_OK;
   }
   return HOH_E_ARG;
@@ -402,6 +407,7 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
   memset(&j, 0, sizeof(j));
   j.speed = speed;
   j.decodable = c->decodable;
+  j.chain_tables = c->chain_tables;
   j.spt = speed ? SPT_S : SK_PER_TILE;
   j.rgb = d_rgb; j.W = W; j.H = H;
   j.xt = xt; j.yt = yt; j.tw = tw; j.th = th;
@@ -857,6 +863,7 @@ int encode_streams_impl(hoh_ctx* c, const uint16_t* d_syms, const uint64_t* off,
   j.cap = ~0ull;
   j.spt = 1;
   j.decodable = c->decodable;                 // k_tables: no lossy raw table (Q4)
+  j.chain_tables = c->chain_tables;
   if (hipMemcpyAsync(c->streams.p, st.data(), st.size() * sizeof(StreamInfo), hipMemcpyHostToDevice, s) != hipSuccess) return HOH_E_HIP;
   if (hipMemsetAsync(c->misc.p, 0, 64, s) != hipSuccess) return HOH_E_HIP;
   launch_tables(j, nstreams, s);

@@ -25,6 +25,11 @@ static inline int hoh_knob_env(const char* name, int def) { const char* e = gete
 #define HOH_FAST_STRIDE HOH_FAST_RANGE
 #endif
 #define HOH_SEG 256               // decode checkpoint spacing (symbols)
+// the pb-15 plane chain's hot window: this many consecutive symbols' table entries per stream sit
+// in LDS (k_rans_enc.hip, HOT; k_tables picks the window).  <= 63: the packed 16-bit slot << 10
+#ifndef CHAIN_HOT_K
+#define CHAIN_HOT_K 32
+#endif
 #define HOH_MAX_TILE_W 65535
 #define HOH_LZ_WINDOW 64          // -s0 seek distance 6 -> 1 << 6 pixels back (choh.cpp:125, lz.hpp:20)
 
@@ -97,8 +102,13 @@ struct StreamInfo {
                           //   3: a kept trial that stores its words in the trial pool; 4: the
                           //   layer's final stream whose words a stored trial already holds)
   uint32_t hist_src;      // 0: count the symbols; k + 1: the histogram of stream k
-  uint32_t wlo, whi;      // size-only trials: bounds on words (k_tables, from the code length)
+  // size-only trials (sizeonly != 0 in k_tables): bounds on words, from the code length.  Real
+  // prob_bits-15 fast streams: the hot window [hot_lo, hot_lo + CHAIN_HOT_K) of largest mass (ties:
+  // the lowest) and that mass in units of 2^-pb.  The record stays 112 bytes (tests/checklib.py).
+  union { uint32_t wlo; uint32_t hot_lo; };
+  union { uint32_t whi; uint32_t hot_mass; };
 };
+static_assert(sizeof(StreamInfo) == 112, "mirrored by tests/checklib.py");
 
 struct TileInfo {
   int32_t x0, y0, w, h;   // tile rectangle inside the image
@@ -186,6 +196,7 @@ struct EncodeJob {
   uint32_t lz_cap;        // symbols per LZ stream slot
   int speed;              // cruncher_mode (-sN)
   int decodable;          // HOH_OPT_DECODABLE: every layer carries the whole stream its header describes
+  int chain_tables;       // HOH_OPT_CHAIN_TABLES: 0 auto, 1 LDS hot window, 2 global gathers (pb-15 chains)
   int spt;                // streams per tile: SK_PER_TILE (-s0) or SPT_S
   // arenas
   uint16_t* sym;          // residual planes + LZ symbols

@@ -7,7 +7,9 @@
 //  * one stream per lane, 64 streams per wave; the symbol tables (16-B entries: 1/f as
 //    f64, f, c) are gathered from global memory (L2-resident, ~8 KB per stream) one 8-symbol
 //    block ahead through 32-bit offsets from one scalar base (two symbol offsets per packed
-//    16-bit shift);
+//    16-bit shift); in batches the pb-15 plane chains read the 32 most probable consecutive
+//    symbols' entries of each stream from LDS instead (HOT below): a gather is one L1 access per
+//    lane, and that address path is what chains sharing a CU with other work run out of;
 //  * the quotient floor(x/f) of the reciprocal step is computed exactly with two f64
 //    multiplications by 1/f rounded up one ulp (the high word first, then remainder*2^32 +
 //    low word, both < 2^53: exact floors), which is mathematically identical to the Alverson
@@ -33,6 +35,7 @@
 #define WIN_PITCH (WIN + 1)
 #endif
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // one EncFast as a 16-B aligned LDS access
 
 // plane index -> stream: [0, na) through map a, then map b (e.g. the sub-green planes of every
 // tile first, the rarely present indexed planes after them, so idle lanes share few waves)
@@ -61,6 +64,63 @@ __device__ __forceinline__ void lookup8(EncFast* e, uint4 sy, const char* tb, ui
   offs8(o, sy, base);
 #pragma unroll
   for (int k = 0; k < 8; ++k) e[k] = ent(tb, o[k]);
+}
+
+// HOT (the pb-15 plane chains, HOH_OPT_CHAIN_TABLES): each lane's CHAIN_HOT_K entries of its
+// stream's hot window [hot_lo, hot_lo + K) (k_tables) sit in LDS behind the output windows, entry
+// (k, lane) at (k * 64 + lane) * 16: the bank of a 16-B read is set by lane mod 16, so a
+// ds_read_b128 is conflict-free in each of its 16-lane groups whatever k the lanes hold.  The
+// global gather is 64 L1 accesses per instruction, and the L1 address path is what the chains
+// saturate with several images in flight.
+#define HOT_BYTES (CHAIN_HOT_K * 64 * 16)
+static_assert(CHAIN_HOT_K >= 1 && CHAIN_HOT_K <= 63 && CHAIN_HOT_K <= HOH_FAST_RANGE, "slot << 10 fits 16 bits");
+static_assert((WIN_PITCH * 4 * 64) % 16 == 0, "the hot tables start 16-B aligned");
+
+// LDS byte addresses of the hot entries of 8 packed u16 symbols (d = sym - hot_lo, slot =
+// min(d, K - 1): a symbol below the window wraps to a large d), and whether any of the 8 misses
+__device__ __forceinline__ bool hot_offs8(uint32_t* o, uint4 w, us2 lo2, uint32_t base) {
+  const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+  const us2 top = (us2)(CHAIN_HOT_K - 1);
+  us2 mx = (us2)(0);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const us2 dk = __builtin_bit_cast(us2, d[k]) - lo2;
+    mx = __builtin_elementwise_max(mx, dk);
+    const uint32_t t = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(dk, top) << (us2)(10));
+    uint32_t lo;
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD"
+        : "=v"(lo) : "v"(t), "v"(base));
+    o[2 * k] = lo;
+    o[2 * k + 1] = base + (t >> 16);
+  }
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(mx, top)) != __builtin_bit_cast(uint32_t, mx);
+}
+
+// the entries of 8 symbols: eight ds_read_b128; if any lane of the wave misses in this block (a
+// branch the wave skips otherwise), those lanes load the missed entries from the global table
+// under their exec mask, as ent() does: the table's own bytes either way
+__device__ __forceinline__ void hot_lookup8(EncFast* e, uint4 sy, us2 lo2, const unsigned char* lds, uint32_t hbase,
+                                            const char* tb, uint32_t tbase) {
+  uint32_t o[8];
+  const bool miss = hot_offs8(o, sy, lo2, hbase);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    // one 16-B load, its fields taken from the vector (a bit cast of the whole splits the load)
+    const u32x4 v = *(const u32x4*)__builtin_assume_aligned(lds + o[k], 16);
+    e[k].inv = __builtin_bit_cast(double, ((uint64_t)v.y << 32) | v.x);
+    e[k].f = v.z;
+    e[k].c = v.w;
+  }
+  if (__any(miss)) {
+    const uint32_t d[4] = {sy.x, sy.y, sy.z, sy.w};
+    uint32_t g[8];
+    offs8(g, sy, tbase);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const us2 dk = __builtin_bit_cast(us2, d[k >> 1]) - lo2;
+      if (dk[k & 1] >= CHAIN_HOT_K) e[k] = ent(tb, g[k]);
+    }
+  }
 }
 
 struct Coder {
@@ -187,13 +247,13 @@ __device__ __forceinline__ void ckpt(const Coder& c, Checkpoint* ck, uint32_t k)
   ck[k] = p;
 }
 
-template <int KIND, bool WIDE>
+template <int KIND, bool WIDE, bool HOT>
 __device__ __forceinline__ void rans_fast_run(const EncodeJob& j, uint32_t sid, const StreamInfo& st);
 
 // One lane per stream, 64 streams per wave, one wave per workgroup: block blk of a launch.
 // WIDE: each lane's table through its own 64-bit address (jobs whose tables pass 4 GB: batched
 // -s>=1 encodes); otherwise 32-bit offsets from one scalar base (the -s0 chains)
-template <int KIND, bool WIDE = false>
+template <int KIND, bool WIDE = false, bool HOT = false>
 __device__ __forceinline__ void rans_fast_body(const EncodeJob& j, int nplane, SidMap ma, int na, SidMap mb, int blk) {
   const int lane = threadIdx.x & 63;
   // the chain is the critical path of an image: win issue arbitration against co-resident waves
@@ -222,11 +282,11 @@ __device__ __forceinline__ void rans_fast_body(const EncodeJob& j, int nplane, S
   if (st.sizeonly == 2) return;            // pruned trial (k_prune_s): its words are set
   // trials: the storing chain for every lane when the pool is on (storing and counting lanes share
   // a wave: two kinds of chain in one wave would run one after the other)
-  if (KIND == 2 && j.tpool_words) rans_fast_run<3, WIDE>(j, sid, st);
-  else rans_fast_run<KIND, WIDE>(j, sid, st);
+  if (KIND == 2 && j.tpool_words) rans_fast_run<3, WIDE, false>(j, sid, st);
+  else rans_fast_run<KIND, WIDE, HOT && KIND == 0 && !WIDE>(j, sid, st);
 }
 
-template <int KIND, bool WIDE>
+template <int KIND, bool WIDE, bool HOT>
 __device__ __forceinline__ void rans_fast_run(const EncodeJob& j, uint32_t sid, const StreamInfo& st) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr bool GUARD = KIND == 3;
@@ -252,7 +312,45 @@ __device__ __forceinline__ void rans_fast_run(const EncodeJob& j, uint32_t sid, 
   for (uint32_t i = n; i > n - r; i--) stepk<KIND>(c, ent(tb, tbase + (uint32_t)sp[i - 1] * 16u), g);
   if (KIND != 2) flush_win<GUARD>(c);
   if (((nb * 8) % HOH_SEG) == 0 && nb * 8 < n) ckpt(c, ck, nb * 8 / HOH_SEG);
-  if (nb) {
+  if (HOT && nb) {
+    // Hot window in LDS: this lane's K entries (its own column of the wave's region; one wave per
+    // region and a lane reads only what it wrote: no barrier).  hot_lo is clamped so that any
+    // record reads K in-bounds entries; the window only decides which entries come from where.
+    const uint32_t hlo = min(st.hot_lo, (uint32_t)(HOH_FAST_RANGE - CHAIN_HOT_K));
+    const uint32_t hbase = blockDim.x * (WIN_PITCH * 4) + (threadIdx.x >> 6) * HOT_BYTES + lane * 16;
+#pragma unroll
+    for (int k = 0; k < CHAIN_HOT_K; ++k)
+      *(u32x4*)__builtin_assume_aligned(lds + hbase + k * 1024, 16) = __builtin_bit_cast(u32x4, ent(tb, tbase + (hlo + k) * 16u));
+    const us2 lo2 = (us2)((unsigned short)hlo);
+    // Entries looked up ONE 8-symbol block ahead (an LDS read returns within a chain step), one
+    // block's symbols loaded per block, 4 blocks ahead of their lookup.  The miss loads are
+    // conditional, so the compiler's wait before a block's first step counts only the symbol loads
+    // behind them: with none missing, the two youngest symbol loads stay in flight (a lead of 16
+    // steps and more, as in the global loop); a block with a miss waits for that gather.  The
+    // symbol loads are unconditional (past the stream's start they repeat block 0) and the window
+    // is flushed before the lookups of a turn, so no other store or load falls between a lookup
+    // and its use.
+    const uint4* sp4 = (const uint4*)sp;
+    EncFast e0[8], e1[8];
+    auto ld = [&](int b) { return sp4[b > 0 ? b : 0]; };
+    auto look = [&](EncFast* e, const uint4& sy) { hot_lookup8(e, sy, lo2, lds, hbase, tb, tbase); };
+    auto run = [&](const EncFast* e, int b) {
+#pragma unroll
+      for (int k = 7; k >= 0; --k) stepk<KIND>(c, e[k], g);
+      if ((b & (HOH_SEG / 8 - 1)) == 0) ckpt(c, ck, (uint32_t)b * 8 / HOH_SEG);
+    };
+    const int top = (int)nb - 1;
+    uint4 s3 = ld(top), s2 = ld(top - 1), s1 = ld(top - 2), s0 = ld(top - 3);
+    look(e0, s3); s3 = ld(top - 4);
+    for (int b = top; b >= 3; b -= 4) {
+      // entering: e0 = block b (in flight), s2, s1, s0, s3 = the symbols of blocks b-1 .. b-4
+      flush_win<GUARD>(c);
+      look(e1, s2); s2 = ld(b - 5); run(e0, b);
+      look(e0, s1); s1 = ld(b - 6); run(e1, b - 1);
+      look(e1, s0); s0 = ld(b - 7); run(e0, b - 2);
+      look(e0, s3); s3 = ld(b - 8); run(e1, b - 3);
+    }
+  } else if (nb) {
     // table entries gathered 16 steps ahead (two 8-symbol blocks per buffer): with several images
     // in flight the 8 KB-per-stream tables live in MALL/HBM rather than L2, and an 8-step lead
     // left the chain waiting on the gather (15 % of its time even alone; four 8-entry buffers
@@ -306,13 +404,13 @@ __device__ __forceinline__ void rans_fast_run(const EncodeJob& j, uint32_t sid, 
   j.streams[sid].widx_end = c.widx;
 }
 
-template <int KIND, bool WIDE>
+template <int KIND, bool WIDE, bool HOT = false>
 __global__ __launch_bounds__(64) void k_rans_fast(EncodeJob j, int nplane, SidMap ma, int na, SidMap mb, int nblk,
                                                   int rot) {
   // the grid covers every CU; the working blocks are a window rotated per launch so that the
   // chains of images in flight land on different CUs instead of sharing the first ones
   const int blk = (int)((blockIdx.x + gridDim.x - rot) % gridDim.x);
-  if (blk < nblk) rans_fast_body<KIND, WIDE>(j, nplane, ma, na, mb, blk);
+  if (blk < nblk) rans_fast_body<KIND, WIDE, HOT>(j, nplane, ma, na, mb, blk);
 }
 
 // The pb-15 plane chains and, in otherwise idle blocks of the same chip-wide grid, the LZ
@@ -321,11 +419,20 @@ __global__ __launch_bounds__(64) void k_rans_fast(EncodeJob j, int nplane, SidMa
 #ifndef CHAIN_WAVES
 #define CHAIN_WAVES 1
 #endif
-__global__ __launch_bounds__(64 * CHAIN_WAVES) void k_rans_fast01(EncodeJob j, int np0, SidMap a0, int na0, SidMap b0,
-                                                                  int nblk0, int np1, SidMap a1, int na1, SidMap b1,
-                                                                  int nblk1, int rot) {
-  const int blk = (int)((blockIdx.x + gridDim.x - rot) % gridDim.x) * CHAIN_WAVES + (int)(threadIdx.x >> 6);
-  if (blk < nblk0) rans_fast_body<0>(j, np0, a0, na0, b0, blk);
+// HOT: CHAIN_HOT_WAVES chain waves per workgroup, whose LDS request (their windows and hot tables,
+// 80.5 KB at two waves) leaves room for one workgroup per CU: two chains per CU as before, but the
+// two always on different SIMDs of one CU and never beside a third (measured against one-wave
+// workgroups at 2, 3 and 4 per CU and against 3 and 4 waves: profiles/chain_hot/sweeps.txt)
+#ifndef CHAIN_HOT_WAVES
+#define CHAIN_HOT_WAVES 2
+#endif
+template <bool HOT>
+__global__ __launch_bounds__(64 * (HOT ? CHAIN_HOT_WAVES : CHAIN_WAVES)) void k_rans_fast01(
+    EncodeJob j, int np0, SidMap a0, int na0, SidMap b0, int nblk0, int np1, SidMap a1, int na1, SidMap b1, int nblk1,
+    int rot) {
+  constexpr int WAVES = HOT ? CHAIN_HOT_WAVES : CHAIN_WAVES;
+  const int blk = (int)((blockIdx.x + gridDim.x - rot) % gridDim.x) * WAVES + (int)(threadIdx.x >> 6);
+  if (blk < nblk0) rans_fast_body<0, false, HOT>(j, np0, a0, na0, b0, blk);
   else if (blk - nblk0 < nblk1) rans_fast_body<1>(j, np1, a1, na1, b1, blk - nblk0);
 }
 
@@ -418,20 +525,48 @@ static std::atomic<unsigned> g_rot{0};
 #ifndef CHAIN_LDS_DEF
 #define CHAIN_LDS_DEF (CHAIN_WAVES == 1 ? 56 : 81)
 #endif
-static size_t chain_lds(int waves = 1) {
+static size_t chain_lds(int waves = 1, bool hot = false) {
   const int kb = HOH_KNOB(CHAIN_LDS_KB, CHAIN_LDS_DEF);
-  const size_t want = (size_t)(kb > 160 ? 160 : kb) * 1024, win = (size_t)WIN_PITCH * 4 * 64 * waves;
-  return want < win ? win : want;
+  const size_t want = (size_t)(kb > 160 ? 160 : kb) * 1024;
+  const size_t need = ((size_t)WIN_PITCH * 4 * 64 + (hot ? HOT_BYTES : 0)) * waves;
+  return want < need ? need : want;
+}
+// the HOT plane-chain workgroups: what their waves use, unless the knob asks for more
+static size_t chain_hot_lds() {
+  const size_t need = ((size_t)WIN_PITCH * 4 * 64 + HOT_BYTES) * CHAIN_HOT_WAVES;
+  const size_t want = (size_t)std::min(160, HOH_KNOB(CHAIN_HOT_LDS_KB, 0)) * 1024;
+  return want < need ? need : want;
+}
+
+// HOH_OPT_CHAIN_TABLES for a launch of nblk pb-15 chain waves: 1 / 2 pin the LDS hot window / the
+// global gathers.  Auto takes the window for a launch of more chain waves than one 8192^2 image
+// has (64: any batch).  With images in flight the window wins at every launch size (+8-20 %), but a
+// single image's launch alone on the device runs one chain per CU with the L1 path to itself:
+// there the 16-step gather lead hides every entry, and the window's exposed misses cost more than
+// its hits save (natural 8192^2 encode 7.7 -> 9.8 ms; DESIGN.md section 5, profiles/chain_hot/)
+#ifndef CHAIN_HOT_MIN_BLK_DEF
+#define CHAIN_HOT_MIN_BLK_DEF 64
+#endif
+static bool chain_hot(const EncodeJob& j, int nblk) {
+  const int mode = j.chain_tables ? j.chain_tables : HOH_KNOB(CHAIN_TABLES, 0);   // knob: measurement builds
+  if (mode) return mode == 1;
+  return nblk > HOH_KNOB(CHAIN_HOT_MIN_BLK, CHAIN_HOT_MIN_BLK_DEF);
 }
 
 void launch_rans_fast01(const EncodeJob& j, hipStream_t s, int np0, SidMap a0, int na0, SidMap b0, int np1, SidMap a1,
                         int na1, SidMap b1) {
   const int nblk0 = (np0 + 63) / 64, nblk1 = (np1 + 63) / 64;
-  const int nwg = (nblk0 + nblk1 + CHAIN_WAVES - 1) / CHAIN_WAVES;
-  const int grid = std::max(nwg, 1024 / CHAIN_WAVES);
+  const bool hot = chain_hot(j, nblk0);
+  const int waves = hot ? CHAIN_HOT_WAVES : CHAIN_WAVES;
+  const int nwg = (nblk0 + nblk1 + waves - 1) / waves;
+  const int grid = std::max(nwg, 1024 / waves);
   const int rot = (int)((g_rot.fetch_add(1) * 8u * (unsigned)((nwg + 7) / 8)) % (unsigned)grid);
-  hipLaunchKernelGGL(k_rans_fast01, dim3(grid), dim3(64 * CHAIN_WAVES), chain_lds(CHAIN_WAVES), s, j, np0, a0, na0, b0,
-                     nblk0, np1, a1, na1, b1, nblk1, rot);
+  if (hot)
+    hipLaunchKernelGGL(k_rans_fast01<true>, dim3(grid), dim3(64 * CHAIN_HOT_WAVES), chain_hot_lds(), s, j, np0, a0, na0,
+                       b0, nblk0, np1, a1, na1, b1, nblk1, rot);
+  else
+    hipLaunchKernelGGL(k_rans_fast01<false>, dim3(grid), dim3(64 * CHAIN_WAVES), chain_lds(CHAIN_WAVES), s, j, np0, a0,
+                       na0, b0, nblk0, np1, a1, na1, b1, nblk1, rot);
 }
 
 void launch_rans_fast(const EncodeJob& j, int nplane, hipStream_t s, SidMap a, int na, SidMap b, int kind) {
@@ -449,6 +584,8 @@ void launch_rans_fast(const EncodeJob& j, int nplane, hipStream_t s, SidMap a, i
   const bool w = j.tab_wide != 0;
   if (kind == 0) {
     if (w) hipLaunchKernelGGL((k_rans_fast<0, true>), dim3(grid), dim3(64), chain_lds(), s, j, nplane, a, na, b, nblk, rot);
+    else if (chain_hot(j, nblk))
+      hipLaunchKernelGGL((k_rans_fast<0, false, true>), dim3(grid), dim3(64), chain_lds(1, true), s, j, nplane, a, na, b, nblk, rot);
     else hipLaunchKernelGGL((k_rans_fast<0, false>), dim3(grid), dim3(64), chain_lds(), s, j, nplane, a, na, b, nblk, rot);
   } else if (kind == 1) {   // short or few chains (LZ / map streams, the ladder's winners): the window only
     if (w) hipLaunchKernelGGL((k_rans_fast<1, true>), dim3(grid), dim3(64), WIN_PITCH * 4 * 64, s, j, nplane, a, na, b, nblk, rot);

@@ -204,6 +204,21 @@ __global__ __launch_bounds__(64) void k_tables(EncodeJob j, SidMap sm) {
   // range <= 512 (7: its 24-bit multiply of the high quotient; 19: its floors' exactness bound,
   // k_rans_enc.hip step15)
   const bool fast = pb >= 7 && pb <= 19 && range <= HOH_FAST_RANGE && st.fast;
+  // Hot window of the pb-15 chain (k_rans_enc.hip, HOT): the lo in [0, HOH_FAST_RANGE - K] whose K
+  // consecutive symbols hold the most probability mass, ties to the lowest lo.  Each lane walks its
+  // candidates in ascending order, then a wave maximum of the mass and of ~lo among its holders.
+  // (Entries past `range` have f = 1 and are never coded: a window may reach past it.)
+  const bool hot = fast && pb == 15 && !st.sizeonly;
+  uint32_t hot_lo = 0, hot_mass = 0;
+  if (hot) {
+    uint32_t bm = 0, bl = 0;
+    for (uint32_t lo = lane; lo <= HOH_FAST_RANGE - CHAIN_HOT_K; lo += 64) {
+      const uint32_t m = cum[min(lo + CHAIN_HOT_K, range)] - cum[min(lo, range)];
+      if (m > bm) { bm = m; bl = lo; }
+    }
+    hot_mass = wave_max_u32(bm);
+    hot_lo = ~wave_max_u32(bm == hot_mass ? ~bl : 0u);
+  }
   for (uint32_t i = lane; i < (fast ? (uint32_t)HOH_FAST_RANGE : range); i += 64) {
     const uint32_t f = i < range ? fr[i] : 0, c = i < range ? cum[i] : 0;
     if (fast) {
@@ -431,6 +446,7 @@ __global__ __launch_bounds__(64) void k_tables(EncodeJob j, SidMap sm) {
   st.mode = SM_RANS;
   st.wlo = wlo;
   st.whi = whi;
+  if (hot) { st.hot_lo = hot_lo; st.hot_mass = hot_mass; }    // the same words (no trial bounds here)
   j.streams[s] = st;
 }
 

@@ -213,6 +213,10 @@ NOIX_ADAPTIVE, NOIX_LANES, NOIX_MULTI, NOIX_WAVE = -1, 0, 1, 2
 # 1: every encode of the context (any speed, hoh_layer_encode included) writes files that decode;
 # 0 (default): the reference's bytes, whose -s1..-s4 layers cannot be read back
 OPT_DECODABLE = 2
+# where the prob_bits-15 encoder chains read their symbol tables: the stream's hot window in LDS,
+# global gathers only, or (default) chosen per launch; the bytes are the same
+OPT_CHAIN_TABLES = 3
+CHAIN_TABLES_AUTO, CHAIN_TABLES_LDS, CHAIN_TABLES_GLOBAL = 0, 1, 2
 
 
 _CTX = None

@@ -99,6 +99,15 @@ void hoh_reset_kernel_stats(hoh_ctx* ctx);
  *    clamped table instead.
  * Not covered: hoh_mgpu_* (its contexts are its own) and header-only (untiled, Q13) files. */
 #define HOH_OPT_DECODABLE 2
+/* HOH_OPT_CHAIN_TABLES: where the prob_bits-15 encoder chains (every -s0 plane, hoh_encode_entropy
+ * at prob_bits 15) read their symbol tables from.  HOH_CHAIN_TABLES_LDS keeps each stream's 32 most
+ * probable consecutive symbols in LDS and gathers only the others from memory;
+ * HOH_CHAIN_TABLES_GLOBAL gathers every entry from memory; HOH_CHAIN_TABLES_AUTO (default) chooses
+ * per launch.  Every choice gives the same bytes and the same side index. */
+#define HOH_OPT_CHAIN_TABLES 3
+#define HOH_CHAIN_TABLES_AUTO 0
+#define HOH_CHAIN_TABLES_LDS 1
+#define HOH_CHAIN_TABLES_GLOBAL 2
 int hoh_ctx_set_option(hoh_ctx* ctx, int option, int64_t value);
 
 /* ---- image level: `choh in out W H -sN` / `dhoh in out` -------------------------------- */
