@@ -86,6 +86,7 @@ struct hoh_ctx {
   int profiling = 0;
   int noix = HOH_NOIX_ADAPTIVE;  // HOH_OPT_NOIX_DECODER
   int decodable = 0;            // HOH_OPT_DECODABLE
+  int small = 0;                // HOH_OPT_SMALL_IMAGES
   int chain_tables = HOH_CHAIN_TABLES_AUTO;   // HOH_OPT_CHAIN_TABLES
   std::vector<std::string> knames;      // names of the marks recorded by the current call
   std::vector<hipEvent_t> kev;          // event pool, kev[0..nmark) recorded by the current call
@@ -225,6 +226,10 @@ int hoh_ctx_set_option(hoh_ctx* c, int option, int64_t value) {
     case HOH_OPT_DECODABLE:
       if (value != 0 && value != 1) return HOH_E_ARG;
       c->decodable = (int)value;
+      return HOH_OK;
+    case HOH_OPT_SMALL_IMAGES:
+      if (value != 0 && value != 1) return HOH_E_ARG;
+      c->small = (int)value;
       return HOH_OK;
     case HOH_OPT_CHAIN_TABLES:
       if (value < HOH_CHAIN_TABLES_AUTO || value > HOH_CHAIN_TABLES_GLOBAL) return HOH_E_ARG;
@@ -392,10 +397,13 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
                              uint8_t* d_out, size_t cap, uint64_t prefix, int write_table,
                              uint32_t* d_tile_sizes, uint64_t* total_out, hoh_index* idx,
                              hipStream_t s, int speed = 0, uint64_t* d_status = nullptr, int nimg = 1,
-                             uint64_t out_stride = 0) {
+                             uint64_t out_stride = 0, int small_n = 0) {
   const bool async = d_status != nullptr;
   int xt, yt, tw, th;
   hoh_tiling(W, H, &xt, &yt, &tw, &th);
+  // small_n > 0: the image is the stack of small_n small-class images (small_class, hoh_internal.h),
+  // one tile each
+  if (small_n > 0) { xt = 1; yt = small_n; tw = W; th = H / small_n; }
   if (tw > HOH_MAX_TILE_W || (size_t)tw * th > (1u << 24)) return HOH_E_UNSUPPORTED;
   // -s>=1: k_search keeps a tile's 40-px predictor grid (HOH_MAPCAP cells) in LDS and writes a
   // row's residuals four per thread; tiles are < 512 on a side, so only untiled images (one side
@@ -701,6 +709,14 @@ int hoh_encode_image_ix(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int spee
     if (speed && idx) index_clear(idx);
     *out_size = (size_t)total;
     if (printed) *printed = (size_t)total;
+  } else if (c->small && small_class(W, H)) {
+    // HOH_OPT_SMALL_IMAGES: the tile choh codes and discards, kept: header || tile, coded straight
+    // into d_out behind the header (one tile, no table), so out_size is the number choh prints
+    launch_put_bytes(d_out, hb, (int)hl, s);
+    r = encode_tiles_impl(c, d_rgb, W, H, 0, 1, d_out, cap, hl, 1, nullptr, &total, idx, s, speed, nullptr, 1, 0, 1);
+    if (speed && idx) index_clear(idx);
+    *out_size = (size_t)total;
+    if (printed) *printed = (size_t)total;
   } else {
     // choh.cpp:508-520: the single tile is coded and discarded; only the header is written (Q13)
     ScratchFrame f(c);
@@ -724,7 +740,16 @@ int hoh_encode_image_async(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int s
   hipStream_t s = pick(c, stream);
   uint8_t hb[32];
   int xt, yt, tw, th;
-  if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) return HOH_E_UNSUPPORTED;  // header-only files: use the sync call
+  if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) {
+    if (!(c->small && small_class(W, H))) return HOH_E_UNSUPPORTED;     // header-only files: use the sync call
+    const size_t hs = header_fixed(W, H, hb);                           // HOH_OPT_SMALL_IMAGES: header || tile
+    if (cap < hs) return HOH_E_CAP;
+    if (speed && idx) index_clear(idx);
+    launch_put_bytes(d_out, hb, (int)hs, s);
+    uint64_t tot = 0;
+    return encode_tiles_impl(c, d_rgb, W, H, 0, 1, d_out, cap, hs, 1, nullptr, &tot, speed ? nullptr : idx, s, speed,
+                             d_status, 1, 0, 1);
+  }
   size_t hl = header_fixed(W, H, hb);
   hb[hl++] = (uint8_t)(xt - 1);
   hb[hl++] = (uint8_t)(yt - 1);
@@ -740,8 +765,36 @@ int hoh_encode_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int 
                             size_t stride, hoh_index* idx, uint64_t* d_status, void* stream) {
   if (!c || n <= 0 || !d_rgb || !d_out || !d_status || W <= 0 || H <= 0 || speed < 0 || speed > 4) return HOH_E_ARG;
   int xt, yt, tw, th;
-  if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) return HOH_E_UNSUPPORTED;
   const size_t img_bytes = (size_t)W * H * 3;
+  if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) {
+    if (!(c->small && small_class(W, H))) return HOH_E_UNSUPPORTED;
+    // HOH_OPT_SMALL_IMAGES: the n images are the n tiles of their W x n*H stack (small_class), one job
+    // for any H; file i = header || tile i at i * stride, its header written by the stream
+    if (n == 1) return hoh_encode_image_async(c, d_rgb, W, H, speed, d_out, stride, idx, d_status, stream);
+    if ((int64_t)H * n > (1ll << 30) || n > (1 << 24)) return HOH_E_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
+    uint8_t hb[32];
+    const size_t hl = header_fixed(W, H, hb);
+    if (stride < hl) return HOH_E_CAP;
+    launch_put_bytes(d_out, hb, (int)hl, s, n, stride);
+    if (speed && idx) index_clear(idx);               // -s>=1 files get no side index
+    // -s>=1 workspaces grow with the pixels (~8 MB per 256^2 tile) and with the tiles: stacks of at
+    // most speed_stack() tiles and speed_stack() 256^2 tiles' worth of pixels, one after another
+    const int64_t px = (int64_t)speed_stack() * 65536 / ((int64_t)W * H);
+    const int per = speed ? (int)std::max<int64_t>(1, std::min<int64_t>(speed_stack(), px)) : n;
+    for (int i0 = 0; i0 < n; i0 += per) {
+      const int k = std::min(per, n - i0);
+      uint64_t total = 0;
+      const int r = k == 1 ? encode_tiles_impl(c, d_rgb + i0 * img_bytes, W, H, 0, 1, d_out + i0 * stride, stride, hl, 1,
+                                               nullptr, &total, nullptr, s, speed, d_status + 2 * i0, 1, 0, 1)
+                           : encode_tiles_impl(c, d_rgb + i0 * img_bytes, W, H * k, 0, k, d_out + i0 * stride, stride, hl,
+                                               1, nullptr, &total, speed ? nullptr : idx, s, speed, d_status + 2 * i0, k,
+                                               stride, k);
+      if (r) return r;
+    }
+    return HOH_OK;
+  }
   if (n == 1 || !batch_stacks(W, H)) {
     // one image after another on the stream (same bytes); a side index holds one image only
     if (idx && n > 1 && !speed) return HOH_E_UNSUPPORTED;
@@ -1229,4 +1282,5 @@ int ctx_device(hoh_ctx* c) { return c->device; }
 int ctx_cus(hoh_ctx* c) { return c->cus; }
 int ctx_noix(hoh_ctx* c) { return c->noix; }
 int ctx_decodable(hoh_ctx* c) { return c->decodable; }
+int ctx_small(hoh_ctx* c) { return c->small; }
 void ctx_mark(hoh_ctx* c, hipStream_t s, const char* name, bool reset) { prof_mark(c, s, name, reset); }

@@ -116,6 +116,7 @@ int ctx_device(hoh_ctx* c);
 int ctx_cus(hoh_ctx* c);
 int ctx_noix(hoh_ctx* c);                  // HOH_OPT_NOIX_DECODER (include/hoh_ans.h)
 int ctx_decodable(hoh_ctx* c);             // HOH_OPT_DECODABLE
+int ctx_small(hoh_ctx* c);                 // HOH_OPT_SMALL_IMAGES
 void ctx_mark(hoh_ctx* c, hipStream_t s, const char* name, bool reset);
 
 // Per-context device scratch for the host-buffer entry points (encode_entropy, decode_entropy,

@@ -265,6 +265,12 @@ struct EncodeJob {
 // 256-row grid), tile row for tile row.
 inline int batch_stacks(int W, int H) { return (W >= 512 || H >= 512) && W >= 256 && H >= 256 && H % 256 == 0; }
 
+// The small class of HOH_OPT_SMALL_IMAGES: untiled images of at most 511 x 511, whose file is the
+// header followed by the one tile (dhoh.cpp:379).  n of them stack as the n tiles of a W x n*H image
+// with xt = 1, yt = n, tw = W, th = H for ANY H: the geometry is given, not taken from hoh_tiling.
+// Every device size derived from the tile width (LDS rows, rings, bands) holds up to 511.
+inline int small_class(int W, int H) { return W > 0 && H > 0 && W <= 511 && H <= 511; }
+
 // the image of tile t and the base of its file in out
 __host__ __device__ inline int tile_img(const EncodeJob& j, int t) { return j.nimg > 1 ? t / j.img_tiles : 0; }
 // a batch image's file is written only when it fits its stride and none of its tiles failed

@@ -478,11 +478,14 @@ __global__ void k_dmatch_gid(DecJob j, int nstreams) {
   }
 }
 
+// The two aligned dwords around the ABSOLUTE address: base itself may be unaligned (a file inside a
+// batch buffer at an odd stride, decoded on its own), and a load whose address is wave-uniform (the
+// one-lane chains) may be issued as a scalar load, which ignores the address's low two bits.
 __device__ __forceinline__ uint32_t ld_u32_unaligned(const uint8_t* base, uint64_t off) {
-  const uint64_t a = off & ~3ull;
-  const uint32_t* w = (const uint32_t*)(base + a);
+  const uint64_t p = (uint64_t)(uintptr_t)base + off;
+  const uint32_t* w = (const uint32_t*)(uintptr_t)(p & ~3ull);
   const uint32_t lo = w[0];
-  const uint32_t sh = (uint32_t)(off & 3);
+  const uint32_t sh = (uint32_t)(p & 3);
   if (!sh) return lo;
   const uint32_t hi = w[1];
   return __builtin_amdgcn_alignbyte(hi, lo, sh);
@@ -2975,23 +2978,69 @@ int decode_image_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, uint8_t* d_r
   DecJob j;
   memset(&j, 0, sizeof(j));
   j.W = W; j.H = H;
-  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;   // header-only files (Q13)
+  j.in = d_in;
+  j.size = size;
+  j.rgb = d_rgb;
+  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) {
+    // HOH_OPT_SMALL_IMAGES: header || tile (dhoh.cpp:379); the tile starts at the header's end with
+    // its own tiling bytes 0, 0 (k_dparse reads them: anything else is nested tiling).  A file that
+    // ends with the header is choh's header-only file (Q13): no pixels to read
+    if (!ctx_small(c) || !small_class(W, H) || size == p) return 6;
+    if (size < p) return 7;
+    j.xt = j.yt = 1; j.tw = W; j.th = H;
+    j.prefix = p;
+    j.ntiles = 1;
+    return decode_run(c, j, idx, s);
+  }
   j.xt = W / 256; j.yt = H / 256;
   j.tw = (W + j.xt - 1) / j.xt; j.th = (H + j.yt - 1) / j.yt;
   if (p + 2 > size || hb[p] != (uint8_t)(j.xt - 1) || hb[p + 1] != (uint8_t)(j.yt - 1)) return 7;
   j.prefix = p + 2;
   j.ntiles = j.xt * j.yt;
-  j.in = d_in;
-  j.size = size;
-  j.rgb = d_rgb;
   return decode_run(c, j, idx, s);
+}
+
+// HOH_OPT_SMALL_IMAGES, enqueue-only: n small-class W x H files (header || tile, small_class) at
+// d_in + i * stride (n == 1: one file of `stride` bytes) decoded as the n tiles of their W x n*H
+// stack -- xt = 1, yt = n, tw = W, th = H, one job for any H.  k_dhdr checks each file's header,
+// k_dtable (no table to read: one tile per file) puts tile i at i * stride + header, k_dparse reads
+// the tile's own tiling bytes 0, 0 and bounds every read by [i * stride, (i + 1) * stride).
+// {status, W*H*3} per image in d_status.
+static int decode_small_async(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, int W, int H, uint8_t* d_rgb,
+                              size_t cap, const hoh_index* idx, uint64_t* d_status, hipStream_t s) {
+  const uint64_t img = (uint64_t)W * H * 3;
+  if (img > cap) return 2;
+  if ((int64_t)H * n > (1ll << 30) || n > (1 << 24)) return 1;
+  uint8_t hb[16];
+  int p = 0;
+  hb[p++] = 153; hb[p++] = 72; hb[p++] = 79; hb[p++] = 72; hb[p++] = 2; hb[p++] = 8;   // choh.cpp:437-446
+  for (uint32_t v : {(uint32_t)W - 1, (uint32_t)H - 1}) p = (int)hoh_write_varint(hb, (uint32_t)p, v);
+  if (n == 1 && stride == (size_t)p) return 6;     // choh's header-only file (Q13): no pixels to read
+  AsyncDec as;
+  as.hdr[0] = as.hdr[1] = 0;
+  for (int i = 0; i < p; i++) as.hdr[i / 8] |= (uint64_t)hb[i] << (8 * (i % 8));
+  as.hl = p;
+  as.status = d_status;
+  as.bytes = img;
+  DecJob j;
+  memset(&j, 0, sizeof(j));
+  j.W = W; j.H = H * n;                           // the stack
+  j.xt = 1; j.yt = n; j.tw = W; j.th = H;
+  j.prefix = (uint64_t)p;
+  j.ntiles = n;
+  if (n > 1) { j.nimg = n; j.img_tiles = 1; j.in_stride = stride; }
+  j.in = d_in;
+  j.size = (uint64_t)n * stride;
+  j.rgb = d_rgb;
+  return decode_run(c, j, idx, s, &as);
 }
 
 // enqueue-only decode of a W x H file (the caller knows the dimensions; the header is checked on
 // the device); {status, W*H*3} land in d_status
 int decode_image_async_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int W, int H, uint8_t* d_rgb, size_t cap,
                             const hoh_index* idx, uint64_t* d_status, hipStream_t s) {
-  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;   // header-only files: sync call
+  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256))              // header-only files: sync call
+    return ctx_small(c) && small_class(W, H) ? decode_small_async(c, 1, d_in, size, W, H, d_rgb, cap, idx, d_status, s) : 6;
   if ((size_t)W * H * 3 > cap) return 2;
   DecJob j;
   memset(&j, 0, sizeof(j));
@@ -3022,8 +3071,9 @@ int decode_image_async_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int W,
 // one job, every kernel over all n files' tiles); {status, W*H*3} per image in d_status
 int decode_images_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, int W, int H, uint8_t* d_rgb,
                              const hoh_index* idx, uint64_t* d_status, hipStream_t s) {
-  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;
   const size_t img = (size_t)W * H * 3;
+  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256))
+    return ctx_small(c) && small_class(W, H) ? decode_small_async(c, n, d_in, stride, W, H, d_rgb, img, idx, d_status, s) : 6;
   if (n == 1 || !batch_stacks(W, H)) {
     if (index_nstreams(idx) && n > 1) return 6;        // an empty index is no index
     for (int i = 0; i < n; i++) {
@@ -3561,14 +3611,21 @@ int index_build_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, hoh_index* id
   }
   const int W = (int)wv + 1, H = (int)hv + 1;
   *Wp = W; *Hp = H;
-  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) return 6;   // header-only files (Q13)
   DecJob j;
   memset(&j, 0, sizeof(j));
   j.W = W; j.H = H;
-  j.xt = W / 256; j.yt = H / 256;
-  j.tw = (W + j.xt - 1) / j.xt; j.th = (H + j.yt - 1) / j.yt;
-  if (p + 2 > size || hb[p] != (uint8_t)(j.xt - 1) || hb[p + 1] != (uint8_t)(j.yt - 1)) return 7;
-  j.prefix = p + 2;
+  if (!((W >= 512 || H >= 512) && W >= 256 && H >= 256)) {
+    // header-only files (Q13); HOH_OPT_SMALL_IMAGES: header || tile, as decode_image_impl reads it
+    if (!ctx_small(c) || !small_class(W, H) || size == p) return 6;
+    if (size < p) return 7;
+    j.xt = j.yt = 1; j.tw = W; j.th = H;
+    j.prefix = p;
+  } else {
+    j.xt = W / 256; j.yt = H / 256;
+    j.tw = (W + j.xt - 1) / j.xt; j.th = (H + j.yt - 1) / j.yt;
+    if (p + 2 > size || hb[p] != (uint8_t)(j.xt - 1) || hb[p + 1] != (uint8_t)(j.yt - 1)) return 7;
+    j.prefix = p + 2;
+  }
   j.ntiles = j.xt * j.yt;
   j.in = d_in;
   j.size = size;

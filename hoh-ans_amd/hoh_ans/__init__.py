@@ -205,6 +205,8 @@ class Context:
         check(lib().hoh_ctx_set_option(self.h, option, value), "hoh_ctx_set_option")
         if option == OPT_DECODABLE:
             self.decodable = int(value)
+        if option == OPT_SMALL_IMAGES:
+            self.small = int(value)
 
 
 # hoh_ctx_set_option (include/hoh_ans.h)
@@ -217,6 +219,9 @@ OPT_DECODABLE = 2
 # global gathers only, or (default) chosen per launch; the bytes are the same
 OPT_CHAIN_TABLES = 3
 CHAIN_TABLES_AUTO, CHAIN_TABLES_LDS, CHAIN_TABLES_GLOBAL = 0, 1, 2
+# 1: images of at most 511 x 511 are written and read as single-tile files (header || tile) by the
+# image calls, one at a time or as a batch; 0 (default): the reference's header-only file (Q13)
+OPT_SMALL_IMAGES = 4
 
 
 _CTX = None
@@ -666,23 +671,28 @@ class MultiGPU:
 
 # ------------------------------------------------------------------ host-buffer API (reference names)
 
-def choh(rgb, ctx=None, speed=0, decodable=None):
-    """`choh in out W H -sN [--decodable]` on an (H, W, 3) uint8 array -> (file bytes, printed size).
-    decodable=True / False sets OPT_DECODABLE for this call (the context's setting comes back after
-    it); None leaves the context as it is."""
+def choh(rgb, ctx=None, speed=0, decodable=None, small=None):
+    """`choh in out W H -sN [--decodable] [--small-images]` on an (H, W, 3) uint8 array -> (file
+    bytes, printed size).  decodable / small = True / False set OPT_DECODABLE / OPT_SMALL_IMAGES for
+    this call (the context's setting comes back after it); None leaves the context as it is."""
     import torch
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
     H, W, _ = rgb.shape
     d = torch.from_numpy(rgb.reshape(-1)).cuda()
     ctx = ctx or default_ctx()
     was = getattr(ctx, "decodable", 0)
+    was_small = getattr(ctx, "small", 0)
     if decodable is not None:
         ctx.set_option(OPT_DECODABLE, 1 if decodable else 0)
+    if small is not None:
+        ctx.set_option(OPT_SMALL_IMAGES, 1 if small else 0)
     try:
         out, n, printed = encode_image(d, W, H, ctx=ctx, speed=speed)
     finally:
         if decodable is not None:
             ctx.set_option(OPT_DECODABLE, was)
+        if small is not None:
+            ctx.set_option(OPT_SMALL_IMAGES, was_small)
     torch.cuda.synchronize()
     return out[:n].cpu().numpy().tobytes(), printed
 

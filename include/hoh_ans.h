@@ -97,7 +97,9 @@ void hoh_reset_kernel_stats(hoh_ctx* ctx);
  *  - no stream (hoh_encode_entropy included) takes the raw frequency table where it would drop a
  *    frequency's high bits (Q4: a predictor map over a few masks always would); it takes the
  *    clamped table instead.
- * Not covered: hoh_mgpu_* (its contexts are its own) and header-only (untiled, Q13) files. */
+ * Not covered: hoh_mgpu_* (its contexts are its own) and header-only (untiled, Q13) files; with
+ * HOH_OPT_SMALL_IMAGES the small class of untiled images gets a real file, and this option then
+ * applies to its one tile as to any other. */
 #define HOH_OPT_DECODABLE 2
 /* HOH_OPT_CHAIN_TABLES: where the prob_bits-15 encoder chains (every -s0 plane, hoh_encode_entropy
  * at prob_bits 15) read their symbol tables from.  HOH_CHAIN_TABLES_LDS keeps each stream's 32 most
@@ -108,6 +110,32 @@ void hoh_reset_kernel_stats(hoh_ctx* ctx);
 #define HOH_CHAIN_TABLES_AUTO 0
 #define HOH_CHAIN_TABLES_LDS 1
 #define HOH_CHAIN_TABLES_GLOBAL 2
+/* HOH_OPT_SMALL_IMAGES (0 default, 1): images of the SMALL CLASS, W <= 511 and H <= 511 (all of
+ * them untiled, choh.cpp:454-461), are written and read as single-tile files.  At 0 the library
+ * follows the reference: choh codes the one tile, discards it and writes the 8-10 byte header
+ * (SURVEY Q13), and every decode, enqueue-only, batched and index entry point answers
+ * HOH_E_UNSUPPORTED for an untiled shape.  At 1:
+ *  - hoh_encode_image / _ix write header || tile, the tile coded straight into d_out behind the
+ *    header: exactly the bytes the reference's dhoh reads (dhoh.cpp:379 calls decode_tile right after
+ *    the header) and choh throws away, so *out_size == *printed.  The tile is what the context's
+ *    other options make it: without HOH_OPT_DECODABLE the reference's bytes at every speed (palette
+ *    tiles, mode 127, and HOH_E_UNREPRODUCIBLE for non-binary grey included); with it a decodable
+ *    sub-green or RGB tile.  At -s0 _ix records the side index (7 streams);
+ *  - hoh_decode_image / _ix read such a file (header, the tile's own tiling bytes 0 0, one tile of
+ *    W x H) with or without an index.  A file that ends with the header (choh's header-only file)
+ *    stays HOH_E_UNSUPPORTED, nested tiling (nonzero tiling bytes) is HOH_E_UNSUPPORTED, truncation
+ *    or junk HOH_E_CORRUPT;
+ *  - hoh_encode_image_async, hoh_decode_image_async, hoh_encode_images_async and
+ *    hoh_decode_images_async accept the shape.  A batch of n is ONE job for any H: the n images are
+ *    the n tiles of their W x n*H stack; file i lies at i * stride, byte-identical to the
+ *    synchronous call's; one side index serves the batch and equals hoh_index_concat of the n
+ *    single indexes.  -s>=1 batches run in stacks bounded by their pixels;
+ *  - hoh_index_build accepts a small-class file of the -s0 shape.
+ * Untiled shapes OUTSIDE the small class (one side under 256, the other 512 or more) behave as at
+ * 0 on every entry point: the decoder's LDS rows and rings are sized for tiles under 512 wide.
+ * Not covered either way: hoh_decode_region* and hoh_region_cover (HOH_E_UNSUPPORTED for untiled
+ * shapes), hoh_encode_tiles* / hoh_decode_tiles*, hoh_mgpu_*, batches of mixed shapes. */
+#define HOH_OPT_SMALL_IMAGES 4
 int hoh_ctx_set_option(hoh_ctx* ctx, int option, int64_t value);
 
 /* ---- image level: `choh in out W H -sN` / `dhoh in out` -------------------------------- */
@@ -117,8 +145,8 @@ size_t hoh_encode_bound(int W, int H);
 
 /* Replaces choh.cpp:394-527.  speed = cruncher_mode (-s0 .. -s4; choh.cpp:408-427).  Reads
  * W*H*3 interleaved RGB bytes from d_rgb, writes the exact bytes choh writes (header-only for
- * untiled images) to d_out.  *out_size = bytes written; *printed (optional) = the
- * number choh prints (choh.cpp:522).  -s1..-s4 run the predictor search, seek-distance LZ and
+ * untiled images; header || tile for the small class under HOH_OPT_SMALL_IMAGES) to
+ * d_out.  *out_size = bytes written; *printed (optional) = the number choh prints (choh.cpp:522).  -s1..-s4 run the predictor search, seek-distance LZ and
  * prob_bits ladder (layer_encode.hpp:122-392) and get no side index.  Without HOH_OPT_DECODABLE
  * their files are the reference's, undecodable by construction; with it they read
  * back through every decode entry point. */
@@ -180,7 +208,8 @@ int hoh_index_deserialize(hoh_index* idx, const uint8_t* blob, size_t size, void
  * the index hoh_encode_image_ix records for the same file.  HOH_E_UNSUPPORTED (idx empty) for a
  * file the indexed decoder does not cover in full: general tiles (RGB mode, a fourth LZ stream,
  * predictor maps -- every HOH_OPT_DECODABLE -s>=1 file), palette / grey / bitimage tiles, a stream
- * with range > 512 or prob_bits > 15, untiled files.  HOH_E_CORRUPT (idx empty) for a chain that
+ * with range > 512 or prob_bits > 15, untiled files (except the small class under
+ * HOH_OPT_SMALL_IMAGES).  HOH_E_CORRUPT (idx empty) for a chain that
  * runs out of payload or does not end in the initial state, and for any framing error. */
 int hoh_index_build(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, hoh_index* idx, int* W, int* H, void* stream);
 /* dst = the index of n files laid out at i * stride, as hoh_decode_images_async reads them, from
@@ -215,7 +244,9 @@ int hoh_decode_image_ix(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, uint8_t
  * the same stream.  The decoder takes W and H from the caller (the file header is checked on the
  * device: a mismatch gives HOH_E_CORRUPT) and reads at most `size` bytes (a bound suffices, e.g.
  * the encoder's cap).  Header-only (untiled) images return HOH_E_UNSUPPORTED here:
- * use the synchronous calls. */
+ * use the synchronous calls -- unless HOH_OPT_SMALL_IMAGES is set and the shape is of the small
+ * class, which these calls then take like a tiled one (a decode whose `size` is exactly the header's
+ * length, choh's header-only file, still returns HOH_E_UNSUPPORTED). */
 int hoh_encode_image_async(hoh_ctx* ctx, const uint8_t* d_rgb, int W, int H, int speed, uint8_t* d_out,
                            size_t cap, hoh_index* idx, uint64_t* d_status, void* stream);
 int hoh_decode_image_async(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, int W, int H, uint8_t* d_rgb,
@@ -237,7 +268,9 @@ int hoh_decode_image_async(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, int 
  * and no side index (idx, if given, is emptied as in the single-image calls); otherwise tiled
  * images run one after another on the stream (without a side index when n > 1 at -s0:
  * HOH_E_UNSUPPORTED).  Untiled shapes (header-only files) return HOH_E_UNSUPPORTED for
- * any n, as in the single-image async calls: use hoh_encode_image / hoh_decode_image.  The decoder
+ * any n, as in the single-image async calls: use hoh_encode_image / hoh_decode_image -- unless
+ * HOH_OPT_SMALL_IMAGES is set and the shape is of the small class: then the batch is one job for
+ * any H (the n images are the n single tiles of their W x n*H stack), with one side index.  The decoder
  * bounds every parse of file i by [i*stride, (i+1)*stride) (a truncated file reads as corrupt) and
  * reads n*stride bytes of d_hoh at most; in a one-job batch an error in any file marks every
  * image's status. */

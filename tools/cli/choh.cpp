@@ -7,6 +7,8 @@
 // (hoh_mgpu_encode_image: a band of tile rows per device, one RCCL gather); same bytes.
 // `--decodable` (anywhere on the line) sets HOH_OPT_DECODABLE: the file differs from the
 // reference's at -s1..-s4 and can be read back by dhoh (one GPU only).
+// `--small-images` sets HOH_OPT_SMALL_IMAGES: an image of at most 511 x 511 gets header + tile (the
+// bytes the reference codes and discards, which dhoh reads back) instead of the header alone; one GPU only.
 // `--index out.hix` (after the reference's arguments) also writes the encode's side index as a
 // sidecar blob (hoh_index_serialize; the empty index at -s1..-s4) for `dhoh --index`; one GPU only.
 #include <hip/hip_runtime.h>
@@ -30,12 +32,13 @@ static bool read_file(const char* path, std::vector<uint8_t>& b) {
 }
 
 int main(int argc, char** argv) {
-  bool decodable = false;
+  bool decodable = false, small = false;
   const char* hix = nullptr;
   {
     int w = 1;
     for (int i = 1; i < argc; i++) {
       if (!std::strcmp(argv[i], "--decodable")) decodable = true;
+      else if (!std::strcmp(argv[i], "--small-images")) small = true;
       else if (!std::strcmp(argv[i], "--index") && i + 1 < argc) hix = argv[++i];
       else argv[w++] = argv[i];
     }
@@ -48,6 +51,10 @@ int main(int argc, char** argv) {
   }
   if (decodable && devices.size() > 1) {
     std::printf("--decodable encodes on one GPU\n");
+    return 1;
+  }
+  if (small && devices.size() > 1) {
+    std::printf("--small-images encodes on one GPU\n");
     return 1;
   }
   if (argc < 5) {
@@ -76,6 +83,7 @@ int main(int argc, char** argv) {
   hoh_mgpu* mg = nullptr;
   int r = devices.size() > 1 ? hoh_mgpu_create(&mg, (int)devices.size(), devices.data()) : hoh_ctx_create(&ctx, dev0);
   if (r == HOH_OK && decodable) r = hoh_ctx_set_option(ctx, HOH_OPT_DECODABLE, 1);
+  if (r == HOH_OK && small) r = hoh_ctx_set_option(ctx, HOH_OPT_SMALL_IMAGES, 1);
   if (r != HOH_OK) { std::fprintf(stderr, "choh: %s\n", hoh_strerror(r)); return r; }
   const size_t cap = hoh_encode_bound(W, H);
   uint8_t *d_in = nullptr, *d_out = nullptr;

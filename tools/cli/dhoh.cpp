@@ -7,6 +7,8 @@
 // that sidecar (hoh_index_deserialize; choh --index or dhoh --write-index wrote it);
 // `--write-index out.hix` builds the index from the file (hoh_index_build), writes it and decodes
 // with it -- for a file the builder does not cover it writes the empty index and decodes without.
+// The context always has HOH_OPT_SMALL_IMAGES set: a file of at most 511 x 511 that carries its tile
+// (choh --small-images) decodes; the reference's header-only file is refused as before.
 // `--region x,y,w,h` (one GPU, with or without the index options) decodes only the tiles that
 // window touches (hoh_decode_region) and writes its w*h*3 bytes; a malformed region or one not
 // inside the image prints the usage line and returns 1.
@@ -83,6 +85,7 @@ int main(int argc, char** argv) {
   const int dev0 = devices.empty() ? 0 : devices[0];   // --devices 3 / one entry: that GPU
   hoh_mgpu* mg = nullptr;
   r = devices.size() > 1 ? hoh_mgpu_create(&mg, (int)devices.size(), devices.data()) : hoh_ctx_create(&ctx, dev0);
+  if (r == HOH_OK && ctx) r = hoh_ctx_set_option(ctx, HOH_OPT_SMALL_IMAGES, 1);
   if (r != HOH_OK) { std::fprintf(stderr, "dhoh: %s\n", hoh_strerror(r)); return r; }
   const size_t raw = region ? (size_t)rw * rh * 3 : (size_t)W * H * 3;
   uint8_t *d_in = nullptr, *d_rgb = nullptr;
