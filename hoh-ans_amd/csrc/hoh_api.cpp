@@ -278,8 +278,10 @@ extern "C" int hoh_debug_read(hoh_ctx* c, int which, void* dst, size_t bytes) {
   // u16 ranks: tools/scripts/lzsort_check.py); 4: the fingerprints + tile pixel words (k_lzfp)
   // 5: the per-tile kernel counters of the last encode (EncodeJob::dbg, [tile][64] u32)
   // 6: the StreamInfo records of the last encode (tests/test_gpu_check_build.py: ladder bounds)
+  // 7: the LZ candidate bitmap of the last encode ([tile][npix_cap / 64] u64; tests/test_gpu_front_screen.py)
+  // 8: the TileInfo records of the last encode (ncand)
   const Buf& b = which == 0 ? c->matches : which == 3 ? c->lzs : which == 4 ? c->fpb : which == 5 ? c->dbg
-               : which == 6 ? c->streams : c->lzspec;
+               : which == 6 ? c->streams : which == 7 ? c->candbits : which == 8 ? c->tiles : c->lzspec;
   if (bytes > b.n || !b.p) return HOH_E_ARG;
   return hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? HOH_OK : HOH_E_HIP;
 }

@@ -470,8 +470,34 @@ void launch_palette(const EncodeJob& j, hipStream_t s) {
 // that filled it.  Positions whose fingerprint occurs twice get the exact pixel comparison from a
 // per-wave LDS pixel ring.  Candidate words, residuals, histograms and tile flags are the same
 // as k_front's.
+//
+// That is the screen's table mode.  Most content (noise, photographs) has no repeat in most
+// chunks, so a wave starts on a fast path and leaves it only where repeats are dense.  The fast
+// path sets two bits of one word per window, picked by a cheap fingerprint, in a per-wave bit
+// filter of the chunk (a returning LDS OR) and reads the same word of the previous chunk's filter;
+// a lane that finds both bits already set is flagged.  Of equal windows within a chunk all but one are flagged
+// (which one is not is up to the LDS), and a window equal to one of the previous chunk always is.
+// No flagged lane: the candidate word is 0.  A few: each flagged lane f is resolved by the whole
+// wave from registers (the previous, the current and the next chunk's pixels are there): per
+// window pixel i three ballots say where the pixel f + i occurs, and the four shifted ANDed give
+// every window equal to f's; one before f within 64 positions makes f a candidate, and the ones
+// after f inside the chunk are candidates themselves, so the set is exact whichever lane of a
+// group went unflagged.  More than F2_THR flagged lanes: the wave clears its filter bits, builds
+// the previous chunk's table and goes on in table mode, until F2_QUIET consecutive chunks had no
+// candidate; then it empties the table and sets the chunk's filter bits.  The filters alias the
+// tables' LDS (a wave is in one mode at a time and leaves the words it used zero).
 #define F2_TAB 256            // slots of a chunk's fingerprint table (64 keys)
 #define F2_RING 256           // positions of a wave's pixel ring (the exact LZ check)
+#define F2_SCR (2 * (F2_TAB + 1))   // words of a wave's two tables (and as many position words)
+#ifndef F2_MLOG2
+#define F2_MLOG2 14           // log2 of a bit filter's size (two filters of 2^14 bits: the tables' and their position words)
+#endif
+#ifndef F2_THR
+#define F2_THR 4              // more flagged lanes than this in a chunk: table mode
+#endif
+#ifndef F2_QUIET
+#define F2_QUIET 8            // chunks without a candidate before table mode ends
+#endif
 
 __device__ __forceinline__ uint32_t wshl1(uint32_t v, uint32_t old) {   // lane l <- lane l+1, lane 63 <- old
   return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xf, 0xf, false);
@@ -510,12 +536,28 @@ __device__ __forceinline__ void wt_max(uint32_t* pos, uint32_t sl, uint32_t v) {
   __hip_atomic_fetch_max(&pos[sl], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-__global__ __launch_bounds__(NT) void k_front256(EncodeJob j) {
-  __shared__ uint32_t tab[4][2][F2_TAB + 1];        // per wave: two alternating chunk tables
-  // per slot, one word: while its table is the current chunk's, 63 - the key's smallest lane; then
-  // (rewritten after the chunk's checks) the largest lane, for the next chunk's lookups
-  __shared__ uint32_t tpos[4][2][F2_TAB + 1];
+// per-pixel mix of the fast path's window fingerprint (24-bit pixels: a full-rate multiply)
+__device__ __forceinline__ uint32_t pmix(uint32_t v) {
+  const uint32_t m = (uint32_t)__umul24(v, 0x9E3779u);
+  return m ^ (m >> 15);
+}
+
+// kn (knobs builds; the product takes the compile-time values): log2 filter bits | flagged-lane
+// threshold << 5 | start in table mode << 12 | quiet chunks << 13
+__global__ __launch_bounds__(NT) void k_front256(EncodeJob j, uint32_t kn) {
+  // per wave: two alternating chunk tables [2][F2_TAB + 1], then per slot one word
+  // [2][F2_TAB + 1]: while its table is the current chunk's, 63 - the key's smallest lane; then
+  // (rewritten after the chunk's checks) the largest lane, for the next chunk's lookups.  The
+  // fast path's two bit filters are the first 2 << (mlog2 - 5) words.
+  __shared__ uint32_t scr[4][2 * F2_SCR];
   __shared__ uint32_t pring[4][F2_RING];
+#ifdef HOH_KNOBS
+  const uint32_t mlog2 = kn & 31u, thr = (kn >> 5) & 127u, quietk = kn >> 13;
+  bool tmode = (kn >> 12) & 1u;
+#else
+  constexpr uint32_t mlog2 = F2_MLOG2, thr = F2_THR, quietk = F2_QUIET;
+  bool tmode = false;
+#endif
 #ifndef F2_HC
 #define F2_HC 1               // histogram copies (lane & (F2_HC - 1) picks one): fewer same-address atomics
 #endif
@@ -530,8 +572,11 @@ __global__ __launch_bounds__(NT) void k_front256(EncodeJob j) {
   const uint32_t npix = 256u * 256u;
   for (int i = tid; i < F2_HC * (3 * 512 - 256 + 64 * F2_AGG); i += NT) (&hist[0][0])[i] = 0;
   uint32_t* hl = hist[lane & (F2_HC - 1)];
-  for (int i = lane; i < 2 * (F2_TAB + 1); i += 64) tab[wv][i / (F2_TAB + 1)][i % (F2_TAB + 1)] = 0;
-  for (int i = lane; i < 2 * (F2_TAB + 1); i += 64) tpos[wv][i / (F2_TAB + 1)][i % (F2_TAB + 1)] = 0;
+  uint32_t* const sw = scr[wv];
+  for (int i = lane; i < 2 * F2_SCR; i += 64) sw[i] = 0;
+  auto tabp = [&](int c) { return sw + c * (F2_TAB + 1); };
+  auto posp = [&](int c) { return sw + F2_SCR + c * (F2_TAB + 1); };
+  auto fltp = [&](int c) { return sw + ((uint32_t)c << (mlog2 - 5)); };
   if (tid == 0) { s_notgrey = 0; s_ncand = 0; }
   uint16_t* res0 = j.sym + med_plane_off(j, t, 0);
   uint16_t* res1 = j.sym + med_plane_off(j, t, 1);
@@ -565,20 +610,54 @@ __global__ __launch_bounds__(NT) void k_front256(EncodeJob j) {
   int ncand = 0;
   int cb = 0;                                         // table of the current chunk
   uint32_t slot_prev = F2_TAB;                        // this lane's slot in the previous chunk's table
-  // the chunk before the stripe (row ya-1, quarter 3): its windows go into the "previous" table
-  // and its pixels into the ring, so the stripe's first chunk sees all 64 windows behind it
-  if (lz) {
-    if (ya > 0) {
-      const uint32_t pv = prow[3];
-      const uint32_t a1 = wshl1(pv, lane_of(cur[0], 0));
-      const uint32_t a2 = wshl1(a1, lane_of(cur[0], 1));
-      const uint32_t a3 = wshl1(a2, lane_of(cur[0], 2));
-      const uint32_t k = fp32(pv, a1, a2, a3);
-      slot_prev = wt_put(tab[wv][1], k);
-      if (slot_prev < F2_TAB) wt_max(tpos[wv][1], slot_prev, lane);
-      ring[(uint32_t)(ya * 256 - 64 + lane) & (F2_RING - 1)] = pv;
+  // fast path: hash of a chunk's windows, from the chunk's mixes m0 and the next chunk's mn
+  // (equal windows give equal hashes; windows are never shifted as pixels here)
+  auto fbit = [&](uint32_t m0, uint32_t mn) -> uint32_t {
+    const uint32_t m1 = wshl1(m0, lane_of(mn, 0));
+    const uint32_t m2 = wshl1(m1, lane_of(mn, 1));
+    const uint32_t m3 = wshl1(m2, lane_of(mn, 2));
+    const uint32_t f = m0 + __builtin_rotateleft32(m1, 9) + __builtin_rotateleft32(m2, 18) + __builtin_rotateleft32(m3, 27);
+    return (uint32_t)__umul24(f ^ (f >> 13), 0xC2B2AFu);   // (__umul24 returns int)
+  };
+  // a window's filter word (the hash's top bits) and its two bits in it (the next 5 + 5): a lane is
+  // flagged only if both were set, which leaves few false flags to resolve
+  auto fword = [&](uint32_t h) { return h >> (37 - mlog2); };
+  auto fmask = [&](uint32_t h) { return 1u << ((h >> (32 - mlog2)) & 31) | 1u << ((h >> (27 - mlog2)) & 31); };
+  // table mode starts (or the stripe starts in it): the chunk xp before the chunk v at q goes
+  // into the "previous" table (1; the current one is 0) and both into the ring
+  auto table_start = [&](uint32_t q, uint32_t xp, uint32_t v, bool has_prev) {
+    cb = 0;
+    slot_prev = F2_TAB;
+    if (has_prev) {
+      const uint32_t a1 = wshl1(xp, lane_of(v, 0));
+      const uint32_t a2 = wshl1(a1, lane_of(v, 1));
+      const uint32_t a3 = wshl1(a2, lane_of(v, 2));
+      slot_prev = wt_put(tabp(1), fp32(xp, a1, a2, a3));
+      if (slot_prev < F2_TAB) wt_max(posp(1), slot_prev, lane);
+      ring[(q - 64u) & (F2_RING - 1)] = xp;
     }
-    ring[(uint32_t)(ya * 256 + lane) & (F2_RING - 1)] = cur[0];
+    ring[q & (F2_RING - 1)] = v;
+  };
+  int fb = 0;                                         // filter of the current chunk
+  uint32_t wprev = 0;                                 // the filter word this lane set one chunk ago
+  uint32_t quiet = 0;                                 // table mode: chunks without a candidate in a row
+  uint32_t mcur = pmix(cur[0]);
+#ifdef HOH_DEBUG_READ
+  uint32_t n_clean = 0, n_res = 0, n_tab = 0, n_to_tab = 0, n_to_fast = 0;   // EncodeJob::dbg 56..60
+#define F2_COUNT(x) ((x)++)
+#else
+#define F2_COUNT(x) ((void)0)
+#endif
+  // the chunk before the stripe (row ya-1, quarter 3): its windows go into the "previous" filter
+  // (or table), so the stripe's first chunk sees all 64 windows behind it
+  if (lz) {
+    if (tmode) {
+      table_start((uint32_t)(ya * 256 + lane), prow[3], cur[0], ya > 0);
+    } else if (ya > 0) {
+      const uint32_t fh = fbit(pmix(prow[3]), mcur);
+      wprev = fword(fh);
+      atomicOr(&fltp(1)[wprev], fmask(fh));
+    }
   }
   for (int y = ya; y < yb; y++) {
     const bool hasT = y > 0;
@@ -625,84 +704,161 @@ __global__ __launch_bounds__(NT) void k_front256(EncodeJob j) {
       atomicAdd(&hl[768 + rb], 1u);
 #endif
       if (!lz) continue;
-      // the window q .. q+3 (the next chunk's first pixels for the last lanes)
-      const uint32_t nx = k < 3 ? cur[k + 1] : nxt[0];
-      const uint32_t v1 = wshl1(v, lane_of(nx, 0));
-      const uint32_t v2 = wshl1(v1, lane_of(nx, 1));
-      const uint32_t v3 = wshl1(v2, lane_of(nx, 2));
-      ring[(q + 64u) & (F2_RING - 1)] = (q + 64u < npix) ? nx : 0u;   // the ring runs a chunk ahead
+      const uint32_t nx = k < 3 ? cur[k + 1] : nxt[0];   // the next chunk (stale past the tile: only
+      const uint32_t mnx = pmix(nx);                     // windows without `win` see it)
+      const uint32_t q0 = (uint32_t)y * 256u + 64u * k;
       const bool win = q + 3 < npix;
-      const uint32_t hq = win ? fp32(v, v1, v2, v3) : 0u;
-      uint32_t* tc = tab[wv][cb];
-      uint32_t* pc = tpos[wv][cb];
-      const uint32_t* tp = tab[wv][cb ^ 1];
-      const uint32_t* pp = tpos[wv][cb ^ 1];
-#if F2_AGG
-      // lanes holding lane 0's key leave the table work to lane 0 (flat runs give most of a chunk
-      // one key, and same-address LDS atomics serialise): lane 0's min lane is itself, and it writes
-      // the group's max lane for the next chunk
-      const uint32_t h0 = __builtin_amdgcn_readfirstlane(hq);
-      const uint64_t m0 = __ballot(hq == h0);
-      const bool kdup = hq == h0 && lane != 0;
-      uint32_t sq = hq && !kdup ? wt_put(tc, hq) : F2_TAB;
-      {
-        const uint32_t s0 = __builtin_amdgcn_readfirstlane(sq);
-        if (kdup) sq = s0;
-      }
-      if (sq < F2_TAB && !kdup) wt_max(pc, sq, 63u - lane);
-#else
-      const uint32_t sq = hq ? wt_put(tc, hq) : F2_TAB;
-      const bool kdup = false;
-      const uint64_t m0 = 1;
-      if (sq < F2_TAB) wt_max(pc, sq, 63u - lane);
-#endif
-      const uint32_t sp = hq ? wt_find(tp, hq) : F2_TAB;
-      // Equal windows have equal fingerprints, so the windows before q equal to q's can only be
-      // at the positions holding hq: in this chunk at lanes min..lane-1 (the earliest is checked),
-      // in the previous chunk at lanes >= lane (distance <= 64; the latest, i.e. nearest, is
-      // checked).  When a checked window differs (a fingerprint collision) the lane falls back
-      // to the full test over b = 1..64 (lz.hpp:37-42 with offset < 4).
-      const uint32_t fcur = sq < F2_TAB ? 63u - pc[sq] : 64u;
-      const uint32_t lprev = sp < F2_TAB ? pp[sp] : 0u;
-      const bool ccur = fcur < (uint32_t)lane, cprev = sp < F2_TAB && lprev >= (uint32_t)lane;
-      const uint64_t flag = __ballot(ccur || cprev);
       uint64_t word = 0;
-      if (flag) {
-        auto same = [&](uint32_t p) {
-          return ring[p & (F2_RING - 1)] == v && ring[(p + 1) & (F2_RING - 1)] == v1 &&
-                 ring[(p + 2) & (F2_RING - 1)] == v2 && ring[(p + 3) & (F2_RING - 1)] == v3;
-        };
-        const uint32_t q0 = q - lane;
-        bool c = false, full = false;
-        if (ccur || cprev) {
-          c = same(ccur ? q0 + fcur : q0 - 64u + lprev);
-          if (!c && ccur && cprev) c = same(q0 - 64u + lprev);
-          full = !c;
-        }
-        if (__ballot(full)) {
-          if (full) {
-            const uint32_t bmax = q < 64 ? q : 64;
-            for (uint32_t b = 1; b <= bmax && !c; b++) c = same(q - b);
+      if (!tmode) {
+        const uint32_t xp = k ? cur[k - 1] : prow[3];    // the previous chunk, same lane
+        uint32_t* fc = fltp(fb);
+        uint32_t* fp = fltp(fb ^ 1);
+        const uint32_t fh = fbit(mcur, mnx);
+        const uint32_t wi = fword(fh), bits = win ? fmask(fh) : 0u;
+        const uint32_t seen = atomicOr(&fc[wi], bits) | fp[wi];
+        const uint64_t bal = __ballot(win && (seen & bits) == bits);
+        if (bal) {
+          if ((uint32_t)__popcll(bal) <= thr) {
+            F2_COUNT(n_res);
+            const uint64_t winm = __ballot(win);
+            uint64_t cm = 0, todo = bal;
+            while (todo) {
+              const int lf = __builtin_ctzll(todo);
+              todo &= todo - 1;
+              if ((cm >> lf) & 1) continue;            // equal to an earlier flagged lane's: all marked
+              // bit n of mx / my: the window at lane n of the previous / the current chunk equals f's
+              uint64_t mx = q0 ? ~0ull : 0ull, my = ~0ull;   // nothing lies before the tile
+#pragma unroll
+              for (int i = 0; i < 4; i++) {
+                const int l = lf + i;
+                const uint32_t p = l < 64 ? (uint32_t)__builtin_amdgcn_readlane(v, l)
+                                          : (uint32_t)__builtin_amdgcn_readlane(nx, l - 64);
+                const uint64_t X = __ballot(xp == p), Y = __ballot(v == p), Z = __ballot(nx == p);
+                mx &= i ? (X >> i) | (Y << (64 - i)) : X;
+                my &= i ? (Y >> i) | (Z << (64 - i)) : Y;
+              }
+              // before f within 64: the previous chunk's lanes >= lf, this chunk's lanes < lf
+              if ((mx >> lf) | (my & ((1ull << lf) - 1))) cm |= 1ull << lf;
+              cm |= my & (~1ull << lf) & winm;         // after f in this chunk: f lies within 63 before them
+            }
+            word = cm;
+          } else {
+            // dense repeats: leave the filters empty and go on in table mode, from this chunk
+            fc[wi] = 0;
+            fp[wprev] = 0;
+            table_start(q, xp, v, q0 != 0);
+            tmode = true;
+            quiet = 0;
+            F2_COUNT(n_to_tab);
           }
+        } else {
+          F2_COUNT(n_clean);
         }
-        word = __ballot(c);
+        if (!tmode) {
+          fp[wprev] = 0;                                // the previous filter is empty again (reads done)
+          wprev = wi;
+          fb ^= 1;
+        }
       }
-      // this chunk's words turn into the largest lane for the next chunk's lookups (program order
-      // on one address: the fcur reads above come first)
-      if (sq < F2_TAB && !kdup) { pc[sq] = 0; wt_max(pc, sq, lane ? (uint32_t)lane : 63u - (uint32_t)__builtin_clzll(m0)); }
+      if (tmode) {
+        F2_COUNT(n_tab);
+        // the window q .. q+3 (the next chunk's first pixels for the last lanes)
+        const uint32_t v1 = wshl1(v, lane_of(nx, 0));
+        const uint32_t v2 = wshl1(v1, lane_of(nx, 1));
+        const uint32_t v3 = wshl1(v2, lane_of(nx, 2));
+        ring[(q + 64u) & (F2_RING - 1)] = (q + 64u < npix) ? nx : 0u;   // the ring runs a chunk ahead
+        const uint32_t hq = win ? fp32(v, v1, v2, v3) : 0u;
+        uint32_t* tc = tabp(cb);
+        uint32_t* pc = posp(cb);
+        const uint32_t* tp = tabp(cb ^ 1);
+        const uint32_t* pp = posp(cb ^ 1);
+#if F2_AGG
+        // lanes holding lane 0's key leave the table work to lane 0 (flat runs give most of a chunk
+        // one key, and same-address LDS atomics serialise): lane 0's min lane is itself, and it writes
+        // the group's max lane for the next chunk
+        const uint32_t h0 = __builtin_amdgcn_readfirstlane(hq);
+        const uint64_t m0 = __ballot(hq == h0);
+        const bool kdup = hq == h0 && lane != 0;
+        uint32_t sq = hq && !kdup ? wt_put(tc, hq) : F2_TAB;
+        {
+          const uint32_t s0 = __builtin_amdgcn_readfirstlane(sq);
+          if (kdup) sq = s0;
+        }
+        if (sq < F2_TAB && !kdup) wt_max(pc, sq, 63u - lane);
+#else
+        const uint32_t sq = hq ? wt_put(tc, hq) : F2_TAB;
+        const bool kdup = false;
+        const uint64_t m0 = 1;
+        if (sq < F2_TAB) wt_max(pc, sq, 63u - lane);
+#endif
+        const uint32_t sp = hq ? wt_find(tp, hq) : F2_TAB;
+        // Equal windows have equal fingerprints, so the windows before q equal to q's can only be
+        // at the positions holding hq: in this chunk at lanes min..lane-1 (the earliest is checked),
+        // in the previous chunk at lanes >= lane (distance <= 64; the latest, i.e. nearest, is
+        // checked).  When a checked window differs (a fingerprint collision) the lane falls back
+        // to the full test over b = 1..64 (lz.hpp:37-42 with offset < 4).
+        const uint32_t fcur = sq < F2_TAB ? 63u - pc[sq] : 64u;
+        const uint32_t lprev = sp < F2_TAB ? pp[sp] : 0u;
+        const bool ccur = fcur < (uint32_t)lane, cprev = sp < F2_TAB && lprev >= (uint32_t)lane;
+        const uint64_t flag = __ballot(ccur || cprev);
+        if (flag) {
+          auto same = [&](uint32_t p) {
+            return ring[p & (F2_RING - 1)] == v && ring[(p + 1) & (F2_RING - 1)] == v1 &&
+                   ring[(p + 2) & (F2_RING - 1)] == v2 && ring[(p + 3) & (F2_RING - 1)] == v3;
+          };
+          bool c = false, full = false;
+          if (ccur || cprev) {
+            c = same(ccur ? q0 + fcur : q0 - 64u + lprev);
+            if (!c && ccur && cprev) c = same(q0 - 64u + lprev);
+            full = !c;
+          }
+          if (__ballot(full)) {
+            if (full) {
+              const uint32_t bmax = q < 64 ? q : 64;
+              for (uint32_t b = 1; b <= bmax && !c; b++) c = same(q - b);
+            }
+          }
+          word = __ballot(c);
+        }
+        // this chunk's words turn into the largest lane for the next chunk's lookups (program order
+        // on one address: the fcur reads above come first)
+        if (sq < F2_TAB && !kdup) { pc[sq] = 0; wt_max(pc, sq, lane ? (uint32_t)lane : 63u - (uint32_t)__builtin_clzll(m0)); }
+        // empty the previous chunk's table for the next chunk (wave-ordered: every lookup is done)
+        tabp(cb ^ 1)[slot_prev] = 0;                    // slot F2_TAB is a spare: no branch
+        posp(cb ^ 1)[slot_prev] = 0;
+        slot_prev = kdup ? F2_TAB : sq;
+        cb ^= 1;
+        quiet = word ? 0u : quiet + 1u;
+        if (quiet >= quietk) {
+          // repeats have thinned out: empty this chunk's table too and leave its filter bits
+          tabp(cb ^ 1)[slot_prev] = 0;
+          posp(cb ^ 1)[slot_prev] = 0;
+          const uint32_t fh = fbit(mcur, mnx);
+          wprev = fword(fh);
+          fb = 0;
+          atomicOr(&fltp(1)[wprev], win ? fmask(fh) : 0u);
+          tmode = false;
+          F2_COUNT(n_to_fast);
+        }
+      }
       if (lane == 0) cand[q >> 6] = word;
       ncand += lane == 0 ? __popcll(word) : 0;
-      // empty the previous chunk's table for the next chunk (wave-ordered: every lookup is done)
-      uint32_t* tpw = tab[wv][cb ^ 1];
-      tpw[slot_prev] = 0;                             // slot F2_TAB is a spare: no branch
-      tpos[wv][cb ^ 1][slot_prev] = 0;
-      slot_prev = kdup ? F2_TAB : sq;
-      cb ^= 1;
+      mcur = mnx;
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) { prow[k] = cur[k]; cur[k] = nxt[k]; }
     if (y + 2 < 256) load_row(y + 2, nxt);
   }
+#ifdef HOH_DEBUG_READ
+  // per tile: chunks of the fast path without a flagged lane, resolved chunks, table-mode chunks,
+  // switches to table mode and back
+  if (j.dbg && lane == 0) {
+    uint32_t* d = j.dbg + (size_t)t * 64 + 56;
+    atomicAdd(&d[0], n_clean); atomicAdd(&d[1], n_res); atomicAdd(&d[2], n_tab);
+    atomicAdd(&d[3], n_to_tab); atomicAdd(&d[4], n_to_fast);
+  }
+#endif
+#undef F2_COUNT
   if (notgrey) atomicOr(&s_notgrey, 1);
   if (ncand) atomicAdd(&s_ncand, ncand);
   __syncthreads();
@@ -735,7 +891,17 @@ __global__ __launch_bounds__(NT) void k_front256(EncodeJob j) {
 
 void launch_front(const EncodeJob& j, hipStream_t s) {
   hipLaunchKernelGGL(k_colours, dim3(j.ntiles), dim3(NT), 0, s, j);
-  if (j.tw == 256 && j.th == 256) hipLaunchKernelGGL(k_front256, dim3(j.ntiles), dim3(NT), 0, s, j);
+  if (j.tw == 256 && j.th == 256) {
+    // the screen's parameters (knobs builds: sweeps, and the tests' forcing knobs F2_MLOG2 = 6, a
+    // 64-bit filter that flags nearly every chunk, and F2_MODE = 1 fast path only, 2 table mode only)
+    const int mode = HOH_KNOB(F2_MODE, 0);
+    auto clamp = [](int v, int lo, int hi) { return (uint32_t)(v < lo ? lo : v > hi ? hi : v); };
+    const uint32_t mlog2 = clamp(HOH_KNOB(F2_MLOG2, F2_MLOG2), 6, 14);
+    const uint32_t thr = mode == 1 ? 64u : clamp(HOH_KNOB(F2_THR, F2_THR), 0, 64);
+    const uint32_t quiet = mode == 2 ? 0x7ffffu : clamp(HOH_KNOB(F2_QUIET, F2_QUIET), 1, 0x7ffff);
+    const uint32_t kn = mlog2 | thr << 5 | (mode == 2 ? 1u << 12 : 0u) | quiet << 13;
+    hipLaunchKernelGGL(k_front256, dim3(j.ntiles), dim3(NT), 0, s, j, kn);
+  }
   else if (j.tw <= RING_SMALL_MAX_W) hipLaunchKernelGGL(k_front<RING_SMALL>, dim3(j.ntiles), dim3(NT), 0, s, j);
   else if (j.tw <= RING_MAX_W) hipLaunchKernelGGL(k_front<RING>, dim3(j.ntiles), dim3(NT), 0, s, j);
   else hipLaunchKernelGGL(k_front_wide, dim3(j.ntiles), dim3(NT), 0, s, j);
