@@ -224,7 +224,10 @@ def build_tile(tile, layers, mode=128, lz_distance=None, pbs=(15, 15, 15)):
         depth = 9 if (k and mode == 128) else 8
         pidx = np.asarray(pidx, np.uint16)
         tm = np.array([masks[i] for i in pidx], np.uint16)
-        res = orc.predict_all(planes[k].astype(np.uint16), depth, xt, yt, tm)[nuke == 0]
+        if xt == 1 and yt == 1 and masks[0] == 0x0010:         # the -s0 layer: MED on every row, as decode_tile reads it
+            res = orc.predict_fastpath(planes[k].astype(np.uint16), depth).reshape(-1)[nuke == 0]
+        else:
+            res = orc.predict_all(planes[k].astype(np.uint16), depth, xt, yt, tm)[nuke == 0]
         if xt == 1 and yt == 1:
             hdr = bytes([0x10, 0, 0, masks[0] >> 8, masks[0] & 255])
         else:
