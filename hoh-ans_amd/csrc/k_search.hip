@@ -970,6 +970,30 @@ __global__ __launch_bounds__(64) void k_lzvert(EncodeJob j, int limit) {
   if (lane == 0 && added) atomicAdd(&j.tiles[t].ncand, added);
 }
 
+// The same for the posting-list tiles k_lzvert does not take (small images whose width is no
+// multiple of 64 or is above 256: k_lzsort's screen is horizontal only, and k_lzcand, which walks
+// these tiles' columns itself, does not run beside it): a thread per position without a candidate
+// walks its column up from the first row beyond the window.
+__global__ __launch_bounds__(NT) void k_lzvert_any(EncodeJob j, int limit) {
+  const int t = blockIdx.y, lane = threadIdx.x & 63;
+  const TileInfo ti = j.tiles[t];
+  const uint32_t npix = (uint32_t)ti.w * ti.h, w = ti.w, q = blockIdx.x * NT + threadIdx.x;
+  if (lzvert_ok(w, ti.h)) return;
+  const uint32_t* F = j.fpb + (size_t)t * j.npix_cap;
+  uint64_t* cand = j.candbits + (size_t)t * (j.npix_cap / 64);
+  const uint32_t f = q < npix ? F[q] : 0u;
+  bool c = false;
+  if (f && !((cand[q >> 6] >> (q & 63)) & 1)) {
+    const uint32_t bm = q < (uint32_t)limit ? q : (uint32_t)limit, vlim = min(65536u, q);
+    for (uint32_t b = (bm / w + 1) * w; b <= vlim && !c; b += w) c = F[q - b] == f;
+  }
+  const uint64_t m = __ballot(c);                                      // the wave's 64 positions: one word
+  if (lane == 0 && m) {
+    cand[q >> 6] |= m;
+    atomicAdd(&j.tiles[t].ncand, (uint32_t)__popcll(m));
+  }
+}
+
 __global__ __launch_bounds__(NT) void k_lzcand(EncodeJob j, int limit, int ring, int mode, uint32_t mw, int lzc_nowalk) {
   extern __shared__ uint32_t fr[];
   uint32_t* ht = fr + ring;                                            // window tables (LZC_TAB)
@@ -2259,6 +2283,9 @@ void encode_speed_s(const EncodeJob& j, hipStream_t s, const SideStream& side, v
       hipLaunchKernelGGL(k_lzcand, dim3(j.ntiles), dim3(NT), lds, sl, j, limit, lring, mode, mw, HOH_KNOB(LZC_NOWALK, 0));
     }
     hipLaunchKernelGGL(k_lzvert, dim3(4, j.ntiles), dim3(64), 0, sl, j, limit);
+    // posting-list tiles are one size (256 x 256, or the small images of a batch)
+    if (j.lzs && !lzvert_ok((uint32_t)j.tw, (uint32_t)j.th))
+      hipLaunchKernelGGL(k_lzvert_any, dim3((j.npix_cap + NT - 1) / NT, j.ntiles), dim3(NT), 0, sl, j, limit);
     int rp = 1;
     while (rp < limit + 324) rp <<= 1;
     // Four segment walks per tile (stitched as in k_lz), each with a pixel ring of up to

@@ -43,6 +43,7 @@ class CheckLib:
         L.hoh_encode_bound.restype = C.c_size_t
         L.hoh_encode_bound.argtypes = [C.c_int, C.c_int]
         L.hoh_debug_read.argtypes = [vp, C.c_int, vp, C.c_size_t]
+        L.hoh_ctx_set_option.argtypes = [vp, C.c_int, C.c_int64]
         self.L = L
         self.h = vp()
         r = L.hoh_ctx_create(C.byref(self.h), 0)
@@ -53,6 +54,10 @@ class CheckLib:
         if self.h:
             self.L.hoh_ctx_destroy(self.h)
             self.h = C.c_void_p()
+
+    def set_option(self, option, value):
+        r = self.L.hoh_ctx_set_option(self.h, option, value)
+        assert r == 0, "hoh_ctx_set_option(%d, %d): %d" % (option, value, r)
 
     def natural(self, W, H, seed, torch):
         t = torch.empty(W * H * 3, dtype=torch.uint8, device="cuda")
