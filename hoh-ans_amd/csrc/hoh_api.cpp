@@ -76,6 +76,10 @@ struct hoh_ctx {
   hipStream_t own = nullptr;
   SideStream side;              // -s>=1: the LZ screen beside the predictor search (created on first use)
   Buf dbg;                      // measurement builds (HOH_DEBUG_READ): per-tile kernel counters
+#ifdef HOH_DEBUG_READ
+  size_t dbg_search = 0, dbg_search_off = 0;   //   and behind them the last -s>=1 encode's search scratch (bytes, offset)
+  size_t dbg_maps = 0, dbg_pinfo = 0;          //   then its predictor map symbols (bytes); bytes of its PlaneInfo records
+#endif
   Buf idx8, fpb, pinfo, lg;     // -s>=1 workspaces (fpb: fingerprints, then the tile-major pixels)
   Buf lzs;                      // -s>=2: LZ posting lists (k_lzsort): sorted positions + ping-pong (then the sorted fingerprints) + ranks
   uint32_t lg_key[4] = {0, 0, 0, 0};
@@ -280,6 +284,26 @@ extern "C" int hoh_debug_read(hoh_ctx* c, int which, void* dst, size_t bytes) {
   // 6: the StreamInfo records of the last encode (tests/test_gpu_check_build.py: ladder bounds)
   // 7: the LZ candidate bitmap of the last encode ([tile][npix_cap / 64] u64; tests/test_gpu_front_screen.py)
   // 8: the TileInfo records of the last encode (ncand)
+  // 9: the search scratch of the last -s1..-s4 encode as each search pass left it:
+  //    [pass][tile][plane]{ent[512], cost[HOH_MAPCAP][14]} f64 (pass 1 only at -s3 / -s4; the
+  //    snapshot after pass 0 then holds the refined weights beside pass 0's costs)
+  if (which == 9) {
+    if (!c->dbg.p || !c->dbg_search || bytes > c->dbg_search) return HOH_E_ARG;
+    return hipMemcpy(dst, (const uint8_t*)c->dbg.p + c->dbg_search_off, bytes, hipMemcpyDeviceToHost) == hipSuccess
+               ? HOH_OK : HOH_E_HIP;
+  }
+  // 10: the predictor map symbols k_search wrote in the last -s1..-s4 encode, [tile][plane][HOH_MAPCAP]
+  //     u16: a cell's rank among the masks its plane uses; 11: its PlaneInfo records [tile][plane]
+  //     (used_bits names those masks)
+  if (which == 10) {
+    if (!c->dbg.p || !c->dbg_maps || bytes > c->dbg_maps) return HOH_E_ARG;
+    return hipMemcpy(dst, (const uint8_t*)c->dbg.p + c->dbg_search_off + c->dbg_search, bytes, hipMemcpyDeviceToHost) == hipSuccess
+               ? HOH_OK : HOH_E_HIP;
+  }
+  if (which == 11) {
+    if (!c->pinfo.p || !c->dbg_pinfo || bytes > c->dbg_pinfo) return HOH_E_ARG;
+    return hipMemcpy(dst, c->pinfo.p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? HOH_OK : HOH_E_HIP;
+  }
   const Buf& b = which == 0 ? c->matches : which == 3 ? c->lzs : which == 4 ? c->fpb : which == 5 ? c->dbg
                : which == 6 ? c->streams : which == 7 ? c->candbits : which == 8 ? c->tiles : c->lzspec;
   if (bytes > b.n || !b.p) return HOH_E_ARG;
@@ -510,7 +534,12 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
     j.ckpt = index_ckpt_buf(idx);
   }
 #ifdef HOH_DEBUG_READ
-  if ((e = ensure(c->dbg, (size_t)ntiles * 64 * 4))) return e;
+  // the counters, then (-s>=1) the search scratch after each of up to two search passes
+  c->dbg_search = speed ? 2 * (size_t)ntiles * HOH_DBG_SEARCH_BYTES : 0;
+  c->dbg_search_off = hoh_dbg_search_off(ntiles);
+  c->dbg_maps = speed ? hoh_dbg_map_bytes(ntiles) : 0;
+  c->dbg_pinfo = speed ? (size_t)ntiles * HOH_NPLANE_S * sizeof(PlaneInfo) : 0;
+  if ((e = ensure(c->dbg, c->dbg_search_off + c->dbg_search + c->dbg_maps))) return e;
   j.dbg = (uint32_t*)c->dbg.p;
   if (hipMemsetAsync(j.dbg, 0, (size_t)ntiles * 64 * 4, s) != hipSuccess) return HOH_E_HIP;
 #endif

@@ -49,6 +49,16 @@ enum { KS_LZ = 0,          // 4 LZ streams (lz.hpp:100-142, backby2 at distance 
 #define HOH_NPLANE_S 6
 #define HOH_MAPCAP 176     // cells of the 40-px grid: ceil(511 / 40)^2 = 169, rounded to 8
 
+#ifdef HOH_DEBUG_READ
+// checking build: the -s>=1 search scratch of a tile (k_search.hip: per plane 512 entropy weights
+// and HOH_MAPCAP x 14 mask costs, f64), copied after each search pass behind the [tile][64] counters
+// of the context's debug buffer (hoh_debug_read 9)
+#define HOH_DBG_SEARCH_BYTES ((size_t)HOH_NPLANE_S * (512 + HOH_MAPCAP * 14) * 8)
+inline size_t hoh_dbg_search_off(int ntiles) { return (size_t)ntiles * 64 * 4; }
+// behind the two passes' scratch: the predictor map symbols of every plane, [tile][plane][HOH_MAPCAP] u16
+inline size_t hoh_dbg_map_bytes(int ntiles) { return (size_t)ntiles * HOH_NPLANE_S * HOH_MAPCAP * 2; }
+#endif
+
 struct PlaneInfo {         // one -s>=1 layer (layer_encode.hpp:11-412)
   uint32_t present;
   uint32_t depth;

@@ -2322,7 +2322,26 @@ void encode_speed_s(const EncodeJob& j, hipStream_t s, const SideStream& side, v
       if (walk_multi(npred)) hipLaunchKernelGGL(k_search_walk_multi, gw, dim3(64), 0, s, j, npred, ncmax);
       else hipLaunchKernelGGL(k_search_walk, gw, dim3(64), 0, s, j, npred, ncmax);
       hipLaunchKernelGGL(k_search, gs, dim3(NT), sizeof(SearchLds), s, j, 1, pass);
+#ifdef HOH_DEBUG_READ
+      // checking build: every tile's search scratch as this pass left it, behind the counters
+      // (hoh_debug_read 9: [pass][tile][plane]{ent[512], cost[HOH_MAPCAP][14]}; after pass 0 of
+      // -s>=3 the weights are already the refined ones, the costs still pass 0's)
+      static_assert(HOH_DBG_SEARCH_BYTES == HOH_NPLANE_S * SCR_STRIDE * 8 && HOH_DBG_SEARCH_BYTES <= LZC_MAP_OFF, "snapshot = the scratch");
+      // (a failed copy stays the thread's last HIP error: the caller's hipGetLastError after this
+      // function turns it into HOH_E_HIP, so hoh_debug_read never serves a snapshot that was not taken)
+      if (j.dbg)
+        (void)hipMemcpy2DAsync((uint8_t*)j.dbg + hoh_dbg_search_off(j.ntiles) + (size_t)pass * j.ntiles * HOH_DBG_SEARCH_BYTES,
+                               HOH_DBG_SEARCH_BYTES, j.tab_gen, TAB_TILE_BYTES, HOH_DBG_SEARCH_BYTES, (size_t)j.ntiles,
+                               hipMemcpyDeviceToDevice, s);
+#endif
     }
+#ifdef HOH_DEBUG_READ
+    // and the predictor maps k_search's last pass wrote ([tile][plane][HOH_MAPCAP] u16 ranks among the
+    // masks used, PlaneInfo::used_bits: hoh_debug_read 10 and 11)
+    if (j.dbg)
+      (void)hipMemcpyAsync((uint8_t*)j.dbg + hoh_dbg_search_off(j.ntiles) + 2 * (size_t)j.ntiles * HOH_DBG_SEARCH_BYTES,
+                           j.sym + map_sym_off(j, 0, 0), hoh_dbg_map_bytes(j.ntiles), hipMemcpyDeviceToDevice, s);
+#endif
   }
   mark(mc, "search");
   if (fork && (!joined || hipStreamWaitEvent(s, side.join, 0) != hipSuccess)) (void)hipStreamSynchronize(sl);

@@ -23,6 +23,14 @@ u32p = C.POINTER(C.c_uint32)
 szp = C.POINTER(C.c_size_t)
 
 
+class Report(C.Structure):
+    """or_report (oracle/hoh_oracle.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("xt", "yt", "ncell", "npred", "npass", "range", "branch", "winner", "valid",
+                                         "stale")] + \
+               [("bound", C.c_int64), ("med_size", C.c_int64), ("size", C.c_int64 * 8), ("possible", C.c_int64),
+                ("layer_size", C.c_int64)]
+
+
 def build():
     """Compile the oracle (always) and the reference harness (when /root/reference exists)."""
     so = os.path.join(HERE, "liboracle.so")
@@ -90,6 +98,10 @@ def lib():
         L.or_dhoh.restype = C.c_long
         L.or_dhoh.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.or_esym_init.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.or_layer_report.restype = C.c_long
+        L.or_layer_report.argtypes = [u16p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
+                                      C.POINTER(Report), C.POINTER(C.c_double), C.POINTER(C.c_double), u8p]
+        L.or_pixel_report.argtypes = [u16p, C.c_int, C.c_int, C.c_int, u8p, u8p]
         _LIB = L
     return _LIB
 
@@ -269,6 +281,46 @@ def layer_encode(plane, depth, speed, nuke=None):
     if r < 0:
         raise OracleError(r)
     return out[:r].tobytes()
+
+
+def layer_report(plane, depth, speed, nuke=None):
+    """What layer_encode decided on the way (or_layer_report: the code or_layer_encode runs) -> dict:
+    layer (bytes, or None), error (0 or the oracle's code), xt, yt, ncell, npred, npass, ent
+    [npass][512], cost [npass][ncell][14], pidx [npass][ncell], bound, med_size, size {prob_bits:
+    bytes, 12..19}, branch (+1 / -1 / 0), winner (prob_bits, 0 = the MED stream, -1 = none), valid,
+    stale, possible."""
+    plane = np.ascontiguousarray(plane, dtype=np.uint16)
+    h, w = plane.shape
+    n = w * h
+    L = lib()
+    out = np.empty(L.or_entropy_bound(n, 1 << depth, 31) + 4096, np.uint8)
+    nk = None if nuke is None else np.ascontiguousarray(nuke, dtype=np.uint8)
+    rep = Report()
+    ent = np.zeros((2, 512), np.float64)
+    cost = np.zeros((2, 169, 14), np.float64)
+    pidx = np.zeros((2, 169), np.uint8)
+    assert (w + 39) // 40 * ((h + 39) // 40) <= 169, (w, h)
+    r = L.or_layer_report(_p(plane, u16p), n, w, h, depth, speed, None if nk is None else _p(nk, u8p), _p(out, u8p),
+                          C.byref(rep), _p(ent, C.POINTER(C.c_double)), _p(cost, C.POINTER(C.c_double)),
+                          _p(pidx, u8p))
+    assert r == rep.layer_size
+    T, P = rep.ncell, rep.npass
+    return dict(layer=out[:r].tobytes() if r >= 0 else None, error=0 if r >= 0 else int(r), xt=rep.xt, yt=rep.yt,
+                ncell=T, npred=rep.npred, npass=P, ent=ent[:P].copy(),
+                cost=cost.reshape(-1)[:P * T * 14].reshape(P, T, 14).copy(),
+                pidx=pidx.reshape(-1)[:P * T].reshape(P, T).copy(), bound=rep.bound, med_size=rep.med_size,
+                size={12 + k: int(rep.size[k]) for k in range(8)} if rep.branch else {}, branch=rep.branch,
+                winner=rep.winner, valid=bool(rep.valid), stale=bool(rep.stale), possible=rep.possible)
+
+
+def pixel_report(plane, depth):
+    """-> (first-least predictor index, two smallest errors equal) per pixel of the whole-plane walk"""
+    plane = np.ascontiguousarray(plane, dtype=np.uint16)
+    h, w = plane.shape
+    first = np.empty((h, w), np.uint8)
+    tie = np.empty((h, w), np.uint8)
+    lib().or_pixel_report(_p(plane, u16p), w, h, depth, _p(first, u8p), _p(tie, u8p))
+    return first, tie.astype(bool)
 
 
 def dhoh(data):

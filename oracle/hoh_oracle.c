@@ -512,8 +512,8 @@ size_t or_predict_section(const uint16_t* d, int w, int h, int depth, int xt, in
 
 /* prediction.hpp:153-229 (channelpredict_all): whole plane with a predictor mask per cell; the
  * best predictor of row y+1 is chosen with row y+1's cell mask, and the last row keeps 0. */
-void or_predict_all(const uint16_t* d, int w, int h, int depth, int xt, int yt, const uint16_t* map,
-                    uint16_t* out) {
+static void predict_all_walk(const uint16_t* d, int w, int h, int depth, int xt, int yt, const uint16_t* map,
+                             uint16_t* out, uint8_t* first, uint8_t* tie) {
   int c = 1 << depth, half = c / 2;
   int tw = (w + xt - 1) / xt, th = (h + yt - 1) / yt;
   int* bp = (int*)malloc(sizeof(int) * w);
@@ -531,10 +531,35 @@ void or_predict_all(const uint16_t* d, int w, int h, int depth, int xt, int yt, 
       L = d[loc];
       bp[x] = 0;
       if (y + 1 < h) bp[x] = best_pred(d[loc], p, map[((y + 1) / th) * xt + x / tw], c);
+      if (first) {                                   /* or_pixel_report: this pixel's sixteen errors */
+        int e1 = 1 << 30, e2 = 1 << 30;
+        for (int j = 0; j < 16; j++) {
+          int e = abs((int)d[loc] - (int)p[j]);
+          if (e < e1) { e2 = e1; e1 = e; }
+          else if (e < e2) e2 = e;
+        }
+        first[loc] = (uint8_t)best_pred(d[loc], p, 0xffff, c);
+        tie[loc] = (uint8_t)(e1 == e2);
+      }
     }
   }
   free(bp);
   free(top);
+}
+
+void or_predict_all(const uint16_t* d, int w, int h, int depth, int xt, int yt, const uint16_t* map,
+                    uint16_t* out) {
+  predict_all_walk(d, w, h, depth, xt, yt, map, out, NULL, NULL);
+}
+
+/* or_predict_all's own walk (one cell, every predictor allowed) with, per pixel, the first
+ * predictor of least error over all sixteen -- the best predictor that walk keeps for the pixels
+ * below and to the right -- and whether the two smallest errors (of two predictors) are equal */
+void or_pixel_report(const uint16_t* d, int w, int h, int depth, uint8_t* first, uint8_t* tie) {
+  const uint16_t all = 0xffff;
+  uint16_t* out = (uint16_t*)malloc(2 * (size_t)w * h + 2);
+  predict_all_walk(d, w, h, depth, 1, 1, &all, out, first, tie);
+  free(out);
 }
 
 /* unprediction.hpp:6-91 (unpredict_all) for any predictor map: the inverse of or_predict_all,
@@ -622,6 +647,28 @@ static long encode_u8(const uint8_t* v, size_t n, uint8_t* out) {
   return r;
 }
 
+/* seen[p] = 1 when the 12 bytes of pixels p..p+3 also occur at some q < p (0 for the last three
+ * positions, which have no whole window): sorted by (window, position), equal windows are neighbours */
+static __thread const uint8_t* lz_sort_px;   /* qsort has no context argument; callers run on several threads */
+static int lz_win_cmp(const void* a, const void* b) {
+  uint32_t i = *(const uint32_t*)a, j = *(const uint32_t*)b;
+  int c = memcmp(lz_sort_px + 3 * (size_t)i, lz_sort_px + 3 * (size_t)j, 12);
+  return c ? c : (i > j) - (i < j);
+}
+static uint8_t* lz_seen_before(const uint8_t* s, size_t npix) {
+  uint8_t* seen = (uint8_t*)calloc(npix ? npix : 1, 1);
+  if (npix < 5) return seen;
+  size_t nw = npix - 3;
+  uint32_t* ix = (uint32_t*)malloc(nw * 4);
+  for (size_t i = 0; i < nw; i++) ix[i] = (uint32_t)i;
+  lz_sort_px = s;
+  qsort(ix, nw, 4, lz_win_cmp);
+  for (size_t k = 1; k < nw; k++)
+    if (!memcmp(s + 3 * (size_t)ix[k], s + 3 * (size_t)ix[k - 1], 12)) seen[ix[k]] = 1;
+  free(ix);
+  return seen;
+}
+
 /* lz.hpp:6-170 */
 long or_find_lz_rgb(const uint8_t* s, size_t size, int w, int h, uint8_t* lz_out, uint8_t* nuke,
                     int distance, int bonus) {
@@ -634,10 +681,15 @@ long or_find_lz_rgb(const uint8_t* s, size_t size, int w, int h, uint8_t* lz_out
   uint8_t* bb = (uint8_t*)malloc(cap);
   uint8_t* bb2 = (uint8_t*)malloc(cap);
   size_t nf = 0, nl = 0, nb = 0, nb2 = 0;
+  /* A match counts from 4 + bonus >= 4 pixels on (bonus >= 0), and needs window(p) == window(p - back): a position whose
+   * 4-pixel window occurs nowhere before it is searched in vain (longest < 4 has no effect), so
+   * the search is skipped there.  Same matches, only sooner on tiles without repeats. */
+  uint8_t* seen = lz_seen_before(s, npix);
+  if (bonus < 0) memset(seen, 1, npix);    /* shorter matches would count: search everywhere (no caller does) */
   int since = 0;
   for (size_t p = 0; p < npix; p++) {
     int longest = 0, best = -1;
-    for (int back = 1; back <= limit && (long)p - back >= 0; back++) {
+    for (int back = 1; seen[p] && back <= limit && (long)p - back >= 0; back++) {
       int off = 0;
       while (p + off < npix && pix_eq(s, p + off, p + off - back) && off < 259) off++;
       if (off > longest) {
@@ -646,7 +698,7 @@ long or_find_lz_rgb(const uint8_t* s, size_t size, int w, int h, uint8_t* lz_out
         if (off == 259) break;
       }
     }
-    if (longest < 259 && distance > 8) {                            /* lz.hpp:54-74 */
+    if (seen[p] && longest < 259 && distance > 8) {                 /* lz.hpp:54-74 */
       for (int back = w; back <= (1 << 16) && (long)p - back >= 0; back += w) {
         int off = 0;
         while (p + off < npix && pix_eq(s, p + off, p + off - back) && off < 259) off++;
@@ -685,7 +737,7 @@ long or_find_lz_rgb(const uint8_t* s, size_t size, int w, int h, uint8_t* lz_out
   }
   r = (long)bp;
 out:
-  free(fut); free(len); free(bb); free(bb2);
+  free(fut); free(len); free(bb); free(bb2); free(seen);
   return r;
 }
 
@@ -704,15 +756,19 @@ static void entropy_table(const uint16_t* res, size_t n, int range, double* ent)
   free(fr);
 }
 
-/* layer_encode.hpp:176-203: per cell, the first stock mask of least estimated cost */
+/* layer_encode.hpp:176-203: per cell, the first stock mask of least estimated cost.  cost_out
+ * (may be NULL) gets the T x 14 sums as they were compared (columns >= npred: 0). */
 static void search_cells(const uint16_t* d, int w, int h, int depth, int xt, int yt, int npred,
-                         const double* ent, uint16_t* plist, uint8_t* pidx, uint16_t* scratch) {
+                         const double* ent, uint16_t* plist, uint8_t* pidx, uint16_t* scratch,
+                         double* cost_out) {
   for (int i = 0; i < xt * yt; i++) {
     double best = 99999999999.0;
+    for (int pr = 0; pr < 14; pr++) if (cost_out) cost_out[i * 14 + pr] = 0;
     for (int pr = 0; pr < npred; pr++) {
       size_t k = or_predict_section(d, w, h, depth, xt, yt, i % xt, i / xt, kMasks[pr], scratch);
       double cost = 0;
       for (size_t v = 0; v < k; v++) cost += ent[scratch[v]];
+      if (cost_out) cost_out[i * 14 + pr] = cost;
       if (cost < best) { best = cost; plist[i] = kMasks[pr]; pidx[i] = (uint8_t)pr; }
     }
   }
@@ -723,8 +779,9 @@ static void search_cells(const uint16_t* d, int w, int h, int depth, int xt, int
  * prob_bits 16 vs 15 and three more prob_bits in that direction; the output is `possible_size`
  * bytes of the `permanent` buffer, which is not swapped for the 16/15 pair (Q14), so it may be a
  * prefix of an older stream. */
-long or_layer_encode(const uint16_t* data, size_t n, int w, int h, int depth, int cruncher,
-                     const uint8_t* nuke, uint8_t* out) {
+static long layer_core(const uint16_t* data, size_t n, int w, int h, int depth, int cruncher,
+                       const uint8_t* nuke, uint8_t* out, or_report* rep, double* rent, double* rcost,
+                       uint8_t* rpidx) {
   size_t oi = 0;
   size_t possible = ((size_t)depth * n + ((size_t)depth * n) % 8 + 1024) / 8;   /* :22 */
   const int range = 1 << depth;
@@ -742,10 +799,18 @@ long or_layer_encode(const uint16_t* data, size_t n, int w, int h, int depth, in
   int valid = 0;                                                    /* perm holds a stream */
   long r = or_encode_entropy(clean, nc, (size_t)range, 15, dummy);  /* :106-113 */
   if (r < 0) goto fail;
+  int winner = -1, stale = 0;                                       /* what perm holds; a prefix of it? */
+  if (rep) {
+    memset(rep, 0, sizeof(*rep));
+    rep->range = range;
+    rep->bound = (int64_t)possible;
+    rep->med_size = r;
+  }
   if ((size_t)r < possible) {                                       /* :115-120 */
     possible = (size_t)r;
     uint8_t* x = perm; perm = dummy; dummy = x;
     valid = 1;
+    winner = 0;
   }
   if (cruncher && ((w + 39) / 40 > 1 || (h + 39) / 40 > 1)) {       /* :124-132 */
     int xt = (w + 39) / 40, yt = (h + 39) / 40, T = xt * yt;
@@ -754,13 +819,18 @@ long or_layer_encode(const uint16_t* data, size_t n, int w, int h, int depth, in
     uint16_t* plist = (uint16_t*)malloc(2 * (size_t)T);
     uint8_t* pidx = (uint8_t*)malloc((size_t)T);
     uint16_t* scratch = (uint16_t*)malloc((n ? n : 1) * 2);
-    entropy_table(res, n, range, ent);
-    search_cells(data, w, h, depth, xt, yt, npred, ent, plist, pidx, scratch);
-    or_predict_all(data, w, h, depth, xt, yt, plist, res);          /* :205-214 */
-    if (cruncher > 2) {                                             /* :215-272 */
+    const int npass = cruncher > 2 ? 2 : 1;                         /* :215-272: refined once */
+    if (rep) { rep->xt = xt; rep->yt = yt; rep->ncell = T; rep->npred = npred; rep->npass = npass; }
+    for (int pass = 0; pass < npass; pass++) {
       entropy_table(res, n, range, ent);
-      search_cells(data, w, h, depth, xt, yt, npred, ent, plist, pidx, scratch);
-      or_predict_all(data, w, h, depth, xt, yt, plist, res);
+      search_cells(data, w, h, depth, xt, yt, npred, ent, plist, pidx, scratch,
+                   rcost ? rcost + (size_t)pass * T * 14 : NULL);
+      if (rent) {
+        memset(rent + (size_t)pass * 512, 0, 512 * sizeof(double));
+        memcpy(rent + (size_t)pass * 512, ent, sizeof(double) * range);
+      }
+      if (rpidx) memcpy(rpidx + (size_t)pass * T, pidx, (size_t)T);
+      or_predict_all(data, w, h, depth, xt, yt, plist, res);        /* :205-214 */
     }
     out[oi++] = (uint8_t)(xt - 1);                                  /* :276-277 */
     out[oi++] = (uint8_t)(yt - 1);
@@ -790,24 +860,54 @@ long or_layer_encode(const uint16_t* data, size_t n, int w, int h, int depth, in
     if (t2 < 0) { r = t2; goto fail; }
     int pb0 = t1 < t2 ? 17 : 14, step = t1 < t2 ? 1 : -1;
     long t12 = t1 < t2 ? t1 : t2;
-    if ((size_t)t12 < possible) possible = (size_t)t12;            /* no swap (Q14) */
+    if ((size_t)t12 < possible) { possible = (size_t)t12; stale = 1; }   /* no swap (Q14) */
+    if (rep) {
+      rep->branch = step;
+      rep->size[16 - 12] = t1;
+      rep->size[15 - 12] = t2;
+    }
     for (int k = 0; k < 3; k++) {
       long t = or_encode_entropy(clean, nc, (size_t)range, (uint32_t)(pb0 + step * k), dummy);
       if (t < 0) { r = t; goto fail; }
+      if (rep) rep->size[pb0 + step * k - 12] = t;
       if ((size_t)t < possible) {
         possible = (size_t)t;
         uint8_t* x = perm; perm = dummy; dummy = x;
         valid = 1;
+        winner = pb0 + step * k;
+        stale = 0;
       }
     }
+    if (rep) {                                /* the branch not taken: sizes only, nothing decided */
+      for (int k = 0; k < 3; k++) {
+        rep->size[pb0 - 3 * step - step * k - 12] =        /* an error stays in the report alone */
+            or_encode_entropy(clean, nc, (size_t)range, (uint32_t)(pb0 - 3 * step - step * k), dummy);
+      }
+    }
+  }
+  if (rep) {
+    rep->winner = winner; rep->valid = valid; rep->stale = stale;
+    rep->possible = (int64_t)possible;
   }
   if (!valid) { r = OR_E_UNREPRODUCIBLE; goto fail; }               /* copies garbage */
   memcpy(out + oi, perm, possible);                                 /* :396-398 */
   oi += possible;
   r = (long)oi;
 fail:
+  if (rep) rep->layer_size = r;
   free(res); free(clean); free(bufa); free(bufb);
   return r;
+}
+
+long or_layer_encode(const uint16_t* data, size_t n, int w, int h, int depth, int cruncher,
+                     const uint8_t* nuke, uint8_t* out) {
+  return layer_core(data, n, w, h, depth, cruncher, nuke, out, NULL, NULL, NULL, NULL);
+}
+
+long or_layer_report(const uint16_t* data, size_t n, int w, int h, int depth, int cruncher,
+                     const uint8_t* nuke, uint8_t* out, or_report* rep, double* ent, double* cost,
+                     uint8_t* pidx) {
+  return layer_core(data, n, w, h, depth, cruncher, nuke, out, rep, ent, cost, pidx);
 }
 
 long or_layer_encode_s0(const uint16_t* data, size_t n, int w, int h, int depth, const uint8_t* nuke,

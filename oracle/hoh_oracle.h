@@ -87,6 +87,30 @@ long or_layer_encode(const uint16_t* data, size_t n, int w, int h, int depth, in
 long or_encode_tile(const uint8_t* rgb, int w, int h, int cruncher, uint8_t* out, size_t cap);
 long or_choh(const uint8_t* rgb, int W, int H, int speed, uint8_t* out, size_t cap, size_t* printed);
 
+/* What or_layer_encode decided on the way (tests/designed_search.py): both run the same code.
+ * ent: [npass][512] entropy tables (entries >= range: 0); cost: [npass][ncell][14] mask costs,
+ * summed as search_cells sums them (columns >= npred: 0); pidx: [npass][ncell] chosen stock mask.
+ * Any of the three may be NULL; size them for 2 passes and 169 cells. */
+typedef struct {
+  int32_t xt, yt, ncell, npred, npass;   /* npass 0: no grid (cruncher 0 or a plane of one cell) */
+  int32_t range;
+  int32_t branch;                        /* +1: prob_bits 16 < 15, trials 17 18 19; -1: 14 13 12; 0: no ladder */
+  int32_t winner;                        /* prob_bits of the stream in the permanent buffer; 0: the MED stream; -1: none */
+  int32_t valid;                         /* 0: the reference copies uninitialised bytes (OR_E_UNREPRODUCIBLE) */
+  int32_t stale;                         /* the unswapped 16/15 pair's size cuts the permanent buffer (Q14) */
+  int64_t bound;                         /* layer_encode.hpp:22 */
+  int64_t med_size;                      /* the MED residuals' stream at prob_bits 15 */
+  int64_t size[8];                       /* the final residuals' stream at prob_bits 12..19 (all eight) */
+  int64_t possible;                      /* bytes of the permanent buffer that reach the layer */
+  int64_t layer_size;                    /* or_layer_encode's return */
+} or_report;
+long or_layer_report(const uint16_t* data, size_t n, int w, int h, int depth, int cruncher,
+                     const uint8_t* nuke, uint8_t* out, or_report* rep, double* ent, double* cost,
+                     uint8_t* pidx);
+/* per pixel of or_predict_all's whole-plane walk: the first predictor of least error over all
+ * sixteen, and whether the two smallest errors are equal */
+void or_pixel_report(const uint16_t* data, int w, int h, int depth, uint8_t* first, uint8_t* tie);
+
 /* layer_encode.hpp:11-412, cruncher_mode 0 */
 long or_layer_encode_s0(const uint16_t* data, size_t n, int w, int h, int depth, const uint8_t* nuke,
                         uint8_t* out);

@@ -23,7 +23,15 @@ STREAM_DTYPE = np.dtype([("sym_off", "<u8"), ("slab_off", "<u8"), ("out_off", "<
                          ("expected_stored", "<u8"), ("fast", "<u4"), ("ckpt_off", "<u4"), ("drop", "<u4"),
                          ("clip", "<u4"), ("sizeonly", "<u4"), ("hist_src", "<u4"), ("wlo", "<u4"), ("whi", "<u4")])
 assert STREAM_DTYPE.itemsize == 112
-SM_RANS = 1
+SM_EMPTY, SM_RANS, SM_STORED = 0, 1, 2
+# -s1..-s4 stream kinds and plane slots (hoh_internal.h), the search scratch (k_search.hip)
+KS_MED, KS_FIN, KS_MAP, KS_VAR, SPT_S, NPLANE_S, MAPCAP = 4, 10, 16, 22, 70, 6, 176
+VAR_PB = (16, 15, 17, 18, 19, 14, 13, 12)
+SCR_STRIDE = 512 + MAPCAP * 14
+# PlaneInfo (hoh_internal.h), 56 bytes
+PLANE_DTYPE = np.dtype([(k, "<u4") for k in ("present", "depth", "xt", "yt", "used", "used_bits", "fixed_len", "possible",
+                                             "perm_final", "valid", "size", "limit")] + [("out_off", "<u8")])
+assert PLANE_DTYPE.itemsize == 56
 
 
 class CheckLib:
@@ -83,6 +91,33 @@ class CheckLib:
 
     def streams(self, count):
         return self.read(6, np.zeros(count, STREAM_DTYPE))
+
+    def search_scratch(self, ntiles, npass):
+        """the -s1..-s4 search scratch of the last encode as each search pass left it ->
+        (ent [pass][tile][plane][512], cost [pass][tile][plane][MAPCAP][14]) float64.  Planes: 0 G,
+        1 R', 2 B', 3 indexed, 4 R, 5 B.  Only what the search wrote is defined: a searched plane's
+        first 2^depth weights and its cells' first npred costs; the rest is stale.  After
+        pass 0 of -s3 / -s4 ent is already the refined table (the one pass 1's costs use)."""
+        a = self.read(9, np.zeros((npass, ntiles, NPLANE_S, SCR_STRIDE), np.float64))
+        return a[..., :512], a[..., 512:].reshape(npass, ntiles, NPLANE_S, MAPCAP, 14)
+
+    def search_maps(self, ntiles):
+        """the predictor maps k_search's last pass wrote in the last -s1..-s4 encode -> (PlaneInfo
+        records [tile][plane], chosen stock mask index [tile][plane][MAPCAP], -1 beyond a plane's
+        cells or where it has no grid): the kernel stores a cell's rank among the masks its plane
+        uses (used_bits), as the map stream codes it"""
+        pi = self.read(11, np.zeros((ntiles, NPLANE_S), PLANE_DTYPE))
+        rank = self.read(10, np.zeros((ntiles, NPLANE_S, MAPCAP), np.uint16))
+        idx = np.full(rank.shape, -1, np.int64)
+        for t in range(ntiles):
+            for p in range(NPLANE_S):
+                q = pi[t, p]
+                if q["present"] and q["xt"]:
+                    used = np.array([m for m in range(14) if (int(q["used_bits"]) >> m) & 1])
+                    n = int(q["xt"]) * int(q["yt"])
+                    assert len(used) == int(q["used"]) and int(rank[t, p, :n].max()) < len(used)
+                    idx[t, p, :n] = used[rank[t, p, :n]]
+        return pi, idx
 
 
 def check_posting_lists(fpb, lzs, ntiles, cap):
