@@ -81,6 +81,7 @@ struct hoh_ctx {
   size_t dbg_maps = 0, dbg_pinfo = 0;          //   then its predictor map symbols (bytes); bytes of its PlaneInfo records
 #endif
   Buf idx8, fpb, pinfo, lg;     // -s>=1 workspaces (fpb: fingerprints, then the tile-major pixels)
+  Buf mstage;                   // mixed-shape batches: the encoder's staging surface (k_mgather)
   Buf lzs;                      // -s>=2: LZ posting lists (k_lzsort): sorted positions + ping-pong (then the sorted fingerprints) + ranks
   uint32_t lg_key[4] = {0, 0, 0, 0};
   uint64_t lg_off[4] = {0, 0, 0, 0};
@@ -202,7 +203,7 @@ static void freebuf(Buf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 
 void hoh_ctx_destroy(hoh_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  Buf* all[] = {&c->dbg, &c->idx8, &c->fpb, &c->lzs, &c->pinfo, &c->lg, &c->sym, &c->hist, &c->candbits, &c->matches, &c->lzspec, &c->pal, &c->streams, &c->tiles, &c->hdr,
+  Buf* all[] = {&c->dbg, &c->mstage, &c->idx8, &c->fpb, &c->lzs, &c->pinfo, &c->lg, &c->sym, &c->hist, &c->candbits, &c->matches, &c->lzspec, &c->pal, &c->streams, &c->tiles, &c->hdr,
                 &c->tab_fast, &c->tab_gen, &c->slabs, &c->ckpt, &c->misc, &c->tsizes};
   for (Buf* b : all) freebuf(*b);
   for (Buf& b : c->scr.chunks) freebuf(b);
@@ -390,8 +391,10 @@ static void prof_cb(void* p, const char* name) { ((Prof*)p)->mark(name); }
 
 // -log2(k / n) for k = 0..n+1 and every tile pixel count n of the image (layer_encode.hpp:143),
 // computed once per image shape with the host's log2 so the -s>=1 search sees the reference's
-// exact doubles
-static int ensure_log2_tables(hoh_ctx* c, int W, int H, EncodeJob& j) {
+// exact doubles.  An enqueue-only call may find the previous job of the stream still searching with
+// the tables of another shape: the host waits for the stream before it replaces them (a call
+// sequence of one shape never does).
+static int ensure_log2_tables(hoh_ctx* c, int W, int H, EncodeJob& j, hipStream_t s) {
   const int rw = W - (j.xt - 1) * j.tw, bh = H - (j.yt - 1) * j.th;
   uint32_t ns[4] = {(uint32_t)(j.tw * j.th), (uint32_t)(rw * j.th), (uint32_t)(j.tw * bh), (uint32_t)(rw * bh)};
   uint32_t un[4] = {0, 0, 0, 0};
@@ -407,6 +410,7 @@ static int ensure_log2_tables(hoh_ctx* c, int W, int H, EncodeJob& j) {
       c->lg_off[k] = tab.size();
       for (uint32_t f = 0; f <= un[k] + 1; f++) tab.push_back(f ? -log2((double)f / (double)un[k]) : 0.0);
     }
+    if (hipStreamSynchronize(s) != hipSuccess) return HOH_E_HIP;
     int e = ensure(c->lg, tab.size() * sizeof(double));
     if (e) return e;
     if (hipMemcpy(c->lg.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return HOH_E_HIP;
@@ -423,13 +427,17 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
                              uint8_t* d_out, size_t cap, uint64_t prefix, int write_table,
                              uint32_t* d_tile_sizes, uint64_t* total_out, hoh_index* idx,
                              hipStream_t s, int speed = 0, uint64_t* d_status = nullptr, int nimg = 1,
-                             uint64_t out_stride = 0, int small_n = 0) {
+                             uint64_t out_stride = 0, int small_n = 0, const MixedDims* mx = nullptr,
+                             const uint8_t* mx_src = nullptr) {
   const bool async = d_status != nullptr;
   int xt, yt, tw, th;
   hoh_tiling(W, H, &xt, &yt, &tw, &th);
   // small_n > 0: the image is the stack of small_n small-class images (small_class, hoh_internal.h),
   // one tile each
   if (small_n > 0) { xt = 1; yt = small_n; tw = W; th = H / small_n; }
+  // mx: a mixed-shape batch (-s0, small_n = its n >= 2).  d_rgb is the staging surface of pitch W =
+  // wmax, one slab of hmax rows per image, filled here from the caller's packed images mx_src; tile
+  // i's own w, h come from mx (launch_front_mixed), its header length too (launch_layout_mixed)
   if (tw > HOH_MAX_TILE_W || (size_t)tw * th > (1u << 24)) return HOH_E_UNSUPPORTED;
   // -s>=1: k_search keeps a tile's 40-px predictor grid (HOH_MAPCAP cells) in LDS and writes a
   // row's residuals four per thread; tiles are < 512 on a side, so only untiled images (one side
@@ -474,7 +482,7 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
     if ((e = ensure(c->idx8, (size_t)ntiles * j.npix_cap))) return e;
     if ((e = ensure(c->fpb, (size_t)ntiles * j.npix_cap * 13))) return e;   // fingerprints + pixels + transposed + runs
     if ((e = ensure(c->pinfo, (size_t)ntiles * HOH_NPLANE_S * (sizeof(PlaneInfo) + 8 * 4)))) return e;   // + trial list
-    if ((e = ensure_log2_tables(c, W, H, j))) return e;
+    if ((e = ensure_log2_tables(c, W, H, j, s))) return e;
     j.idx8 = (uint8_t*)c->idx8.p;
     j.fpb = (uint32_t*)c->fpb.p;
     j.tpx = j.fpb + (size_t)ntiles * j.npix_cap;
@@ -563,10 +571,18 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
       hipMemsetAsync(j.candbits, 0, (size_t)ntiles * (j.npix_cap / 64) * 8, s) != hipSuccess) return HOH_E_HIP;
   if (hipMemsetAsync(c->misc.p, 0, 64 + (size_t)nimg * 16, s) != hipSuccess) return HOH_E_HIP;
   prof.mark("memset");
+  if (mx) {
+    launch_mgather(*mx, mx_src, (uint8_t*)d_rgb, s);
+    prof.mark("mgather");
+    launch_mheader(*mx, d_out, out_stride, s);
+    prof.mark("mheader");
+  }
   // knob ENC_STOP = k (measurement, -s0): the encode stops after stage k (1 front, 2 palette, 3 LZ
   // + nuke, 4 tables, 5 chains, 6 rANS generic + finalize, 7 layout + assembly); output invalid
   const int stop = HOH_KNOB(ENC_STOP, 0);
-  launch_front(j, s);            prof.mark("front");
+  if (mx) launch_front_mixed(j, *mx, s);
+  else launch_front(j, s);
+  prof.mark("front");
   if (stop != 1) launch_palette(j, s);
   prof.mark("palette");
   if (speed) {
@@ -598,7 +614,11 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
     if (!stop || stop > 5) { launch_rans_gen(j, (int)S, s); launch_finalize(j, (int)S, s); }
     prof.mark("rans_enc_gen");
     prof.mark("finalize");
-    if (!stop || stop > 6) { launch_layout(j, s); launch_assemble(j, (int)S, s); }
+    if (!stop || stop > 6) {
+      if (mx) launch_layout_mixed(j, *mx, s);
+      else launch_layout(j, s);
+      launch_assemble(j, (int)S, s);
+    }
     prof.mark("layout");
     prof.mark("assemble");
     if (stop) idx = nullptr;
@@ -792,6 +812,42 @@ int hoh_encode_image_async(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int s
                            speed, d_status);
 }
 
+// n images of ONE small-class shape (small_class, hoh_internal.h): the n tiles of their W x n*H
+// stack, one job for any H; file i = header || tile i at i * stride, its header written by the
+// stream.  Behind hoh_encode_images_async under HOH_OPT_SMALL_IMAGES and the equal-shape runs of
+// hoh_encode_mixed_async at -s>=1.
+static int encode_small_batch(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int H, int speed, uint8_t* d_out,
+                              size_t stride, hoh_index* idx, uint64_t* d_status, hipStream_t s) {
+  const size_t img_bytes = (size_t)W * H * 3;
+  if ((int64_t)H * n > (1ll << 30) || n > (1 << 24)) return HOH_E_ARG;
+  (void)hipSetDevice(c->device);
+  uint8_t hb[32];
+  const size_t hl = header_fixed(W, H, hb);
+  if (stride < hl) return HOH_E_CAP;
+  if (speed && idx) index_clear(idx);                 // -s>=1 files get no side index
+  launch_put_bytes(d_out, hb, (int)hl, s, n, stride);
+  if (n == 1) {
+    uint64_t tot = 0;
+    return encode_tiles_impl(c, d_rgb, W, H, 0, 1, d_out, stride, hl, 1, nullptr, &tot, speed ? nullptr : idx, s, speed,
+                             d_status, 1, 0, 1);
+  }
+  // -s>=1 workspaces grow with the pixels (~8 MB per 256^2 tile) and with the tiles: stacks of at
+  // most speed_stack() tiles and speed_stack() 256^2 tiles' worth of pixels, one after another
+  const int64_t px = (int64_t)speed_stack() * 65536 / ((int64_t)W * H);
+  const int per = speed ? (int)std::max<int64_t>(1, std::min<int64_t>(speed_stack(), px)) : n;
+  for (int i0 = 0; i0 < n; i0 += per) {
+    const int k = std::min(per, n - i0);
+    uint64_t total = 0;
+    const int r = k == 1 ? encode_tiles_impl(c, d_rgb + i0 * img_bytes, W, H, 0, 1, d_out + i0 * stride, stride, hl, 1,
+                                             nullptr, &total, nullptr, s, speed, d_status + 2 * i0, 1, 0, 1)
+                         : encode_tiles_impl(c, d_rgb + i0 * img_bytes, W, H * k, 0, k, d_out + i0 * stride, stride, hl,
+                                             1, nullptr, &total, speed ? nullptr : idx, s, speed, d_status + 2 * i0, k,
+                                             stride, k);
+    if (r) return r;
+  }
+  return HOH_OK;
+}
+
 int hoh_encode_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int H, int speed, uint8_t* d_out,
                             size_t stride, hoh_index* idx, uint64_t* d_status, void* stream) {
   if (!c || n <= 0 || !d_rgb || !d_out || !d_status || W <= 0 || H <= 0 || speed < 0 || speed > 4) return HOH_E_ARG;
@@ -799,32 +855,7 @@ int hoh_encode_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int 
   const size_t img_bytes = (size_t)W * H * 3;
   if (!hoh_tiling(W, H, &xt, &yt, &tw, &th)) {
     if (!(c->small && small_class(W, H))) return HOH_E_UNSUPPORTED;
-    // HOH_OPT_SMALL_IMAGES: the n images are the n tiles of their W x n*H stack (small_class), one job
-    // for any H; file i = header || tile i at i * stride, its header written by the stream
-    if (n == 1) return hoh_encode_image_async(c, d_rgb, W, H, speed, d_out, stride, idx, d_status, stream);
-    if ((int64_t)H * n > (1ll << 30) || n > (1 << 24)) return HOH_E_ARG;
-    (void)hipSetDevice(c->device);
-    hipStream_t s = pick(c, stream);
-    uint8_t hb[32];
-    const size_t hl = header_fixed(W, H, hb);
-    if (stride < hl) return HOH_E_CAP;
-    launch_put_bytes(d_out, hb, (int)hl, s, n, stride);
-    if (speed && idx) index_clear(idx);               // -s>=1 files get no side index
-    // -s>=1 workspaces grow with the pixels (~8 MB per 256^2 tile) and with the tiles: stacks of at
-    // most speed_stack() tiles and speed_stack() 256^2 tiles' worth of pixels, one after another
-    const int64_t px = (int64_t)speed_stack() * 65536 / ((int64_t)W * H);
-    const int per = speed ? (int)std::max<int64_t>(1, std::min<int64_t>(speed_stack(), px)) : n;
-    for (int i0 = 0; i0 < n; i0 += per) {
-      const int k = std::min(per, n - i0);
-      uint64_t total = 0;
-      const int r = k == 1 ? encode_tiles_impl(c, d_rgb + i0 * img_bytes, W, H, 0, 1, d_out + i0 * stride, stride, hl, 1,
-                                               nullptr, &total, nullptr, s, speed, d_status + 2 * i0, 1, 0, 1)
-                           : encode_tiles_impl(c, d_rgb + i0 * img_bytes, W, H * k, 0, k, d_out + i0 * stride, stride, hl,
-                                               1, nullptr, &total, speed ? nullptr : idx, s, speed, d_status + 2 * i0, k,
-                                               stride, k);
-      if (r) return r;
-    }
-    return HOH_OK;
+    return encode_small_batch(c, n, d_rgb, W, H, speed, d_out, stride, idx, d_status, pick(c, stream));
   }
   if (n == 1 || !batch_stacks(W, H)) {
     // one image after another on the stream (same bytes); a side index holds one image only
@@ -859,6 +890,67 @@ int hoh_encode_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int 
     if (r) return r;
   }
   return HOH_OK;
+}
+
+size_t hoh_mixed_rgb_bytes(int n, const int32_t* h_wh, uint64_t* offsets) {
+  if (n < 1 || n > HOH_MIXED_MAX_BATCH || !h_wh) return 0;
+  for (int i = 0; i < n; i++)
+    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1])) return 0;
+  uint64_t run = 0;
+  for (int i = 0; i < n; i++) {
+    if (offsets) offsets[i] = run;
+    run += 3ull * (uint64_t)h_wh[2 * i] * (uint64_t)h_wh[2 * i + 1];
+  }
+  if (offsets) offsets[n] = run;
+  return (size_t)run;
+}
+
+// n small-class images of n shapes, packed back to back.  -s0: ONE job -- the n images are the n
+// tiles of an xt = 1, yt = n stack of wmax x hmax slabs on a staging surface (k_mgather fills it),
+// tile i with its own w, h and its own header (MixedDims; k_front_mixed, k_layout_mixed).
+// -s1..-s4: the search keeps at most four log2 tables per job (EncodeJob::lg_n), so maximal runs of
+// consecutive equal shapes go through the uniform small stack (encode_small_batch) one after another.
+int hoh_encode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_rgb, const int32_t* h_wh, int speed, uint8_t* d_out,
+                           size_t stride, hoh_index* idx, uint64_t* d_status, void* stream) {
+  if (!c || n < 1 || n > HOH_MIXED_MAX_BATCH || !d_rgb || !h_wh || !d_out || !d_status || speed < 0 || speed > 4 ||
+      stride == 0)
+    return HOH_E_ARG;
+  for (int i = 0; i < n; i++)
+    if (h_wh[2 * i] <= 0 || h_wh[2 * i + 1] <= 0) return HOH_E_ARG;
+  for (int i = 0; i < n; i++)
+    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1])) return HOH_E_UNSUPPORTED;
+  if (stride < 10) return HOH_E_CAP;                  // the longest header of the class
+  (void)hipSetDevice(c->device);
+  hipStream_t s = pick(c, stream);
+  if (speed && idx) index_clear(idx);                 // -s>=1 files get no side index
+  if (speed || n == 1) {
+    size_t off = 0;
+    for (int i = 0; i < n;) {
+      const int W = h_wh[2 * i], H = h_wh[2 * i + 1];
+      int k = 1;
+      while (i + k < n && h_wh[2 * (i + k)] == W && h_wh[2 * (i + k) + 1] == H) k++;
+      const int r = encode_small_batch(c, k, d_rgb + off, W, H, speed, d_out + (size_t)i * stride, stride,
+                                       speed ? nullptr : idx, d_status + 2 * i, s);
+      if (r) return r;
+      off += (size_t)k * W * H * 3;
+      i += k;
+    }
+    return HOH_OK;
+  }
+  MixedDims d;
+  memset(&d, 0, sizeof(d));
+  d.n = n;
+  for (int i = 0; i < n; i++) {
+    d.wh[2 * i] = h_wh[2 * i]; d.wh[2 * i + 1] = h_wh[2 * i + 1];
+    d.wmax = std::max(d.wmax, d.wh[2 * i]);
+    d.hmax = std::max(d.hmax, d.wh[2 * i + 1]);
+  }
+  d.pitch = d.wmax;
+  int e = ensure(c->mstage, (size_t)d.pitch * d.hmax * n * 3 + 16);
+  if (e) return e;
+  uint64_t total = 0;
+  return encode_tiles_impl(c, (const uint8_t*)c->mstage.p, d.pitch, d.hmax * n, 0, n, d_out, stride, 0, 1, nullptr, &total,
+                           idx, s, 0, d_status, n, stride, n, &d, d_rgb);
 }
 
 int hoh_encode_image(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int speed, uint8_t* d_out, size_t cap,

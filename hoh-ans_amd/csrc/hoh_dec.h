@@ -52,6 +52,7 @@ struct GenTile {
 };
 
 #define HOH_DEC_NBUF 20      // slots 16..18: a region decode's staging surface, whole-file tile table and gid
+                             //   (16 is a mixed-shape batch's staging surface too)
 struct DecWork {
   void* bufs[HOH_DEC_NBUF] = {nullptr};
   size_t sizes[HOH_DEC_NBUF] = {0};
@@ -90,6 +91,16 @@ struct RegionJob {                  // what decode_run needs beside the DecJob o
   uint8_t* dst;                     // the caller's buffer and pitch (bytes)
   size_t pitch;
 };
+
+// Mixed-shape batch decode (hoh_decode_mixed_async, k_mixed.hip): what decode_run needs beside the
+// DecJob.  k_dmixed is the job's front (header check + one DecTile per file, instead of k_dhdr and
+// k_dtable), k_mscatter its back (staging surface -> the caller's packed images).
+struct MixedJob {
+  MixedDims d;
+  uint8_t* dst;                     // the caller's packed images
+};
+void launch_dmixed(const MixedDims& d, const uint8_t* in, uint64_t size, uint64_t stride, DecTile* tiles,
+                   uint32_t* gerr, hipStream_t s);
 
 void dec_free(DecWork& w);
 void noix_release(DecWork& w);

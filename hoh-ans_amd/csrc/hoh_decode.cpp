@@ -28,6 +28,8 @@ int decode_region_async_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, int W
 int decode_regions_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, int W, int H, const int32_t* h_xy,
                               int w, int h, uint8_t* d_rgb, size_t pitch, const hoh_index* idx, uint64_t* d_status,
                               hipStream_t s);
+int decode_mixed_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, const int32_t* h_wh, uint8_t* d_rgb,
+                            const hoh_index* idx, uint64_t* d_status, hipStream_t s);
 int decode_stream_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, size_t* bp, uint16_t* d_out, size_t cap,
                        size_t* n, hipStream_t s);
 int encode_streams_impl(hoh_ctx* c, const uint16_t* d_syms, const uint64_t* off, const uint32_t* cnt, int nstreams,
@@ -147,6 +149,17 @@ int hoh_decode_regions_async(hoh_ctx* c, int n, const uint8_t* d_hoh, size_t str
   (void)hipSetDevice(ctx_device(c));
   return decode_regions_async_impl(c, n, d_hoh, stride, W, H, h_xy, w, h, d_rgb, pitch, idx, d_status,
                                    ctx_stream(c, stream));
+}
+
+int hoh_decode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_hoh, size_t stride, const int32_t* h_wh, uint8_t* d_rgb,
+                           const hoh_index* idx, uint64_t* d_status, void* stream) {
+  if (!c || n < 1 || n > HOH_MIXED_MAX_BATCH || !d_hoh || !h_wh || !d_rgb || !d_status || stride == 0) return HOH_E_ARG;
+  for (int i = 0; i < n; i++)
+    if (h_wh[2 * i] <= 0 || h_wh[2 * i + 1] <= 0) return HOH_E_ARG;
+  for (int i = 0; i < n; i++)
+    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1])) return HOH_E_UNSUPPORTED;
+  (void)hipSetDevice(ctx_device(c));
+  return decode_mixed_async_impl(c, n, d_hoh, stride, h_wh, d_rgb, idx, d_status, ctx_stream(c, stream));
 }
 
 int hoh_decode_image(hoh_ctx* c, const uint8_t* d_hoh, size_t size, uint8_t* d_rgb, size_t cap, int* W, int* H,

@@ -341,6 +341,36 @@ __host__ __device__ inline int map_sid(const SidMap& m, int spt, int i) {
   return m.per ? (i / m.per) * spt + m.base + i % m.per : i;
 }
 
+// Mixed-shape batch (hoh_encode_mixed_async / hoh_decode_mixed_async, k_mixed.hip): n small-class
+// images of n shapes as the n tiles of an xt = 1, yt = n stack of wmax x hmax slabs on a staging
+// surface of one pitch; tile i's own w, h come from this table.  Passed to kernels by value (the
+// shapes are host data of the call; 256 pairs are 2 KB of kernel arguments), so no host buffer
+// outlives the call.  The packed offsets (image i at the sum of 3 * w * h before it) do not fit
+// beside the pairs within 4 KB of arguments: the kernels that need one compute it (mixed_off).
+#define HOH_MIXED_MAX_BATCH 256
+struct MixedDims {
+  int32_t n;                          // images
+  int32_t wmax, hmax;                 // the stack's tile size: the maxima over the images
+  int32_t pitch;                      // staging surface: pixels per row (>= wmax); image i's rows start at i * hmax
+  int32_t wh[2 * HOH_MIXED_MAX_BATCH];
+};
+// bytes of file i's header: magic, format, depth, varint(W - 1), varint(H - 1) (choh.cpp:437-450)
+__host__ __device__ inline uint32_t mixed_hdr_len(const MixedDims& d, int i) {
+  return 6 + hoh_varint_len((uint64_t)d.wh[2 * i] - 1) + hoh_varint_len((uint64_t)d.wh[2 * i + 1] - 1);
+}
+// the header itself (<= 10 bytes for shapes of the small class); returns its length
+__host__ __device__ inline uint32_t mixed_hdr_bytes(const MixedDims& d, int i, uint8_t* o) {
+  o[0] = 153; o[1] = 72; o[2] = 79; o[3] = 72; o[4] = 2; o[5] = 8;
+  uint32_t p = hoh_write_varint(o, 6, (uint64_t)d.wh[2 * i] - 1);
+  return hoh_write_varint(o, p, (uint64_t)d.wh[2 * i + 1] - 1);
+}
+void launch_front_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s);
+void launch_layout_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s);
+void launch_mgather(const MixedDims& d, const uint8_t* packed, uint8_t* stage, hipStream_t s);
+void launch_mheader(const MixedDims& d, uint8_t* out, uint64_t stride, hipStream_t s);
+void launch_mscatter(const MixedDims& d, const uint8_t* stage, uint8_t* packed, const uint32_t* gerr, hipStream_t s);
+void launch_mstatus_dec(const MixedDims& d, const uint32_t* gerr, uint64_t* out, hipStream_t s);
+
 void launch_front(const EncodeJob& j, hipStream_t s);
 void launch_palette(const EncodeJob& j, hipStream_t s);
 void launch_lz(const EncodeJob& j, hipStream_t s);

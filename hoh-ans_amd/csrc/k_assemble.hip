@@ -43,13 +43,17 @@ __device__ uint64_t block_excl_scan(uint64_t v, uint64_t* part, int tid) {
 }
 
 // One workgroup per file: blockIdx.x = the image of a batch (its tiles [tb, te), its file at
-// img * out_stride), else the one file / shard blob.
-__global__ __launch_bounds__(1024) void k_layout(EncodeJob j) {
+// img * out_stride), else the one file / shard blob.  MIXED (a mixed-shape batch, k_layout_mixed):
+// the bytes before the tiles are file img's own header, 8 to 10 bytes, instead of j.prefix; an
+// instantiation of its own, so k_layout compiles as before.
+template <bool MIXED>
+__device__ __forceinline__ void layout_file(const EncodeJob& j, const MixedDims* md) {
   __shared__ uint64_t part[1024];
   __shared__ uint64_t tot_size, tot_vlen;
   const int tid = threadIdx.x, img = blockIdx.x;
   const int tb = j.nimg > 1 ? img * j.img_tiles : 0, te = j.nimg > 1 ? tb + j.img_tiles : j.ntiles;
   const uint64_t fbase = j.nimg > 1 ? (uint64_t)img * j.out_stride : 0;
+  const uint64_t prefix = MIXED ? (uint64_t)mixed_hdr_len(*md, img) : j.prefix;
   if (tid == 0) { tot_size = 0; tot_vlen = 0; }
   __syncthreads();
   // pass 1: tile sizes and the table length
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(1024) void k_layout(EncodeJob j) {
     if (vl) atomicAdd((unsigned long long*)&tot_vlen, (unsigned long long)vl);
   }
   __syncthreads();
-  const uint64_t first = j.prefix + tot_vlen;
+  const uint64_t first = prefix + tot_vlen;
   // pass 2: offsets
   uint64_t carry_s = 0, carry_v = 0;
   for (int base = tb; base < te; base += 1024) {
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(1024) void k_layout(EncodeJob j) {
     if (t < te) {
       TileInfo ti = j.tiles[t];
       ti.off = fbase + first + carry_s + es;
-      ti.pad = (uint32_t)(j.prefix + carry_v + ev);     // where this tile's size varint goes (in its file)
+      ti.pad = (uint32_t)(prefix + carry_v + ev);     // where this tile's size varint goes (in its file)
       j.tiles[t] = ti;
       StreamInfo* st = j.streams + (size_t)t * j.spt;
       uint64_t o = ti.off + 3 + 1;
@@ -134,6 +138,9 @@ __global__ __launch_bounds__(1024) void k_layout(EncodeJob j) {
     else *j.total = first + tot_size;
   }
 }
+
+__global__ __launch_bounds__(1024) void k_layout(EncodeJob j) { layout_file<false>(j, nullptr); }
+__global__ __launch_bounds__(1024) void k_layout_mixed(EncodeJob j, MixedDims d) { layout_file<true>(j, &d); }
 
 __global__ __launch_bounds__(64) void k_tilebytes(EncodeJob j) {
   const int t = blockIdx.x * 64 + threadIdx.x;
@@ -232,6 +239,10 @@ void launch_finalize(const EncodeJob& j, int nstreams, hipStream_t s, SidMap m) 
 
 void launch_layout(const EncodeJob& j, hipStream_t s) {
   hipLaunchKernelGGL(k_layout, dim3(j.nimg > 1 ? j.nimg : 1), dim3(1024), 0, s, j);
+}
+
+void launch_layout_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s) {
+  hipLaunchKernelGGL(k_layout_mixed, dim3(j.nimg), dim3(1024), 0, s, j, d);
 }
 
 void launch_assemble(const EncodeJob& j, int nstreams, hipStream_t s) {

@@ -2129,16 +2129,20 @@ __device__ __forceinline__ void dunpred_lz_tile(const DecJob& j, int t, uint32_t
 // tile), `many` = 1 otherwise (a worker per tile, 32-row bands in 33 KB: four per CU, so the
 // tiles of a natural image, many of them nearly serial, run at once).
 #define LZ_FEW 256
-template <bool FULL, int CH_R>
+#define CH_T 10            // tiles per chain wave (the chain section below)
+template <bool FULL, int CH_R, int PER>
 __device__ void chain_tiles(const DecJob& j, int cls, uint32_t blk);
-template <int CH_R>
+template <int CH_R, int PER>
 __device__ void chain_full(const DecJob& j, int cls, uint32_t blk);
 
 // Workgroups [0, wgrid) take the wavefront tiles; the ones after them the chain tiles (ga
 // workgroups per width class, class 2 only when the edge column is narrower), so both run in
 // the same launch, concurrently, without a second stream.  No static LDS: the chain code
 // addresses the dynamic area from 0.
-template <int CH_R>
+// MIXED (a mixed-shape batch, hoh_decode_mixed_async): class 1 is still one width (the widest), but
+// class 2 holds every other width, and a chain wave walks its tiles with ONE width; so class 2 gets
+// a workgroup per tile there (grid: wgrid + ga + ntiles) instead of CH_T tiles per wave.
+template <int CH_R, bool MIXED>
 __global__ __launch_bounds__(64) void k_dunpred_lz(DecJob j, int br, int many, int wgrid, int ga, int full1, int full2) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lz_lds[];
   if (*(volatile const uint32_t*)j.gerr) return;                      // one load per wave: uniform
@@ -2157,8 +2161,13 @@ __global__ __launch_bounds__(64) void k_dunpred_lz(DecJob j, int br, int many, i
     const uint32_t ci = blockIdx.x;
     const int cls = ci < (uint32_t)ga ? 1 : 2;
     const uint32_t blk = ci - (cls - 1) * ga;
-    if (cls == 1 ? full1 : full2) chain_full<CH_R>(j, cls, blk);
-    else chain_tiles<false, CH_R>(j, cls, blk);
+    if (MIXED && cls == 2) {
+      if (full2) chain_full<CH_R, 1>(j, cls, blk);
+      else chain_tiles<false, CH_R, 1>(j, cls, blk);
+    } else {
+      if (cls == 1 ? full1 : full2) chain_full<CH_R, CH_T>(j, cls, blk);
+      else chain_tiles<false, CH_R, CH_T>(j, cls, blk);
+    }
 #ifdef DEC_DBG
     if (threadIdx.x == 0 && blockIdx.x < 4096) { dbg[2 * blockIdx.x] = (uint32_t)t0; dbg[2 * blockIdx.x + 1] = (uint32_t)__builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -2360,7 +2369,6 @@ __device__ void lds_st4(uint32_t, uint4);
 // store, every step) are conflict-free (a 2 KB stride put all 63 lanes on one bank).
 // CH_T tiles per wave (lanes 3q + p < 3 CH_T): 35 KB of LDS with R = 512, so the launch
 // co-resides with the other kernels of images in flight (21 tiles needed 137 KB, a whole CU's).
-#define CH_T 10
 #define CH_L (3 * CH_T)
 #define CH_QS 164
 __host__ __device__ constexpr uint32_t ch_vs(int R) { return (uint32_t)R * 2 + 4; }
@@ -2375,12 +2383,12 @@ __host__ __device__ constexpr uint32_t ch_smem(int R) { return ch_scr(R) + 16; }
 // residuals it consumed.  16-pixel blocks never straddle a row; their ring slots are contiguous
 // (constant ds offsets); the next step's LDS reads (T, the copy source) are issued before the
 // current step's arithmetic.
-template <int CH_R>
+template <int CH_R, int PER>
 __device__ void chain_full(const DecJob& j, int cls, uint32_t blk) {
   const uint32_t lane = threadIdx.x, q = lane / 3, p = lane - 3 * q;
-  const uint32_t base = blk * CH_T, cnt = *(volatile const uint32_t*)(j.gerr + 6 + cls);
+  const uint32_t base = blk * PER, cnt = *(volatile const uint32_t*)(j.gerr + 6 + cls);
   if (base >= cnt) return;
-  const bool act = lane < CH_L && base + q < cnt;
+  const bool act = lane < 3 * PER && base + q < cnt;
   const int t = (int)j.lzt[(size_t)cls * j.ntiles + base + (act ? q : 0)];
   const DecTile ti = j.tiles[t];
   const uint32_t w = __builtin_amdgcn_readfirstlane(ti.w);             // one width per wave
@@ -2388,7 +2396,7 @@ __device__ void chain_full(const DecJob& j, int cls, uint32_t blk) {
   uint32_t hmax = h;
 #pragma unroll
   for (int o = 32; o; o >>= 1) hmax = max(hmax, (uint32_t)__shfl_xor(hmax, o));
-  if (lane >= CH_L) return;                                            // no rings for these lanes
+  if (lane >= 3 * PER) return;                                         // no rings for these lanes
   const uint32_t c = p ? 512u : 256u, half = c >> 1, cm = c - 1;
   uint16_t* outp = j.dplane + (size_t)(t * 3 + p) * j.npix_cap;
   const uint4* e4 = (const uint4*)outp;
@@ -2546,12 +2554,12 @@ __global__ __launch_bounds__(256) void k_dexpand(DecJob j, int full1, int full2)
 // on its VALU operations, not on LDS round trips.
 // Workgroup `blk` of the chain tiles of width class cls (called from k_dunpred_lz, whose launch
 // has at least ch_smem(CH_R) bytes of dynamic LDS starting at address 0).
-template <bool FULL, int CH_R>
+template <bool FULL, int CH_R, int PER>
 __device__ void chain_tiles(const DecJob& j, int cls, uint32_t blk) {
   const uint32_t lane = threadIdx.x, q = lane / 3, p = lane - 3 * q;
-  const uint32_t base = blk * CH_T, cnt = *(volatile const uint32_t*)(j.gerr + 6 + cls);
+  const uint32_t base = blk * PER, cnt = *(volatile const uint32_t*)(j.gerr + 6 + cls);
   if (base >= cnt) return;
-  const bool act = lane < CH_L && base + q < cnt;
+  const bool act = lane < 3 * PER && base + q < cnt;
   const int t = (int)j.lzt[(size_t)cls * j.ntiles + base + (act ? q : 0)];
   const DecTile ti = j.tiles[t];
   const uint32_t w = __builtin_amdgcn_readfirstlane(ti.w);             // one width per wave
@@ -2559,7 +2567,7 @@ __device__ void chain_tiles(const DecJob& j, int cls, uint32_t blk) {
   uint32_t hmax = h;
 #pragma unroll
   for (int o = 32; o; o >>= 1) hmax = max(hmax, (uint32_t)__shfl_xor(hmax, o));
-  if (lane >= CH_L) return;                                            // no rings for these lanes
+  if (lane >= 3 * PER) return;                                         // no rings for these lanes
   const uint32_t c = p ? 512u : 256u, half = c >> 1, cm = c - 1;
   const DecStream st = j.streams[t * SK_PER_TILE + 3 + p];
   const uint16_t* res = j.dsym + (size_t)(t * 3 + p) * j.plane_cap;
@@ -2949,7 +2957,7 @@ struct AsyncDec {              // enqueue-only decode: expected header bytes and
   uint64_t bytes;               // the status size word on success
 };
 static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s, const AsyncDec* as = nullptr,
-                      const RegionJob* rg = nullptr);
+                      const RegionJob* rg = nullptr, const MixedJob* mx = nullptr);
 void launch_status_dec(const uint32_t* gerr, uint64_t bytes, uint64_t* out, hipStream_t s, int n = 1);
 
 int decode_image_impl(hoh_ctx* c, const uint8_t* d_in, size_t size, uint8_t* d_rgb, size_t cap, int* Wp, int* Hp,
@@ -3333,6 +3341,51 @@ int decode_regions_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t str
   return region_run(c, n, d_in, stride, W, H, h_xy, w, h, d_rgb, pitch, idx, d_status, s);
 }
 
+// Mixed-shape batch (hoh_decode_mixed_async): n small-class files of n shapes (header || tile) at
+// d_in + i * stride decoded as the n tiles of an xt = 1, yt = n stack of wmax x hmax slabs on a
+// staging surface whose pitch is wmax rounded up to 16 pixels (the writers' 16-byte paths);
+// k_mscatter then copies image i to its packed place in d_rgb.  k_dmixed checks each file's header
+// against its own (W, H) and puts tile i at i * stride + header_i; k_dparse bounds every read by
+// [i * stride, (i + 1) * stride).  {status, W_i * H_i * 3} per image in d_status.
+// The chain tiles' second width class (ti.w != tw, k_dlz) holds every width but the widest here:
+// j.we stands for it -- a width that is no multiple of 16 if the class has one (full2 = 0: the
+// multiple-of-16 chain and k_dexpand are for classes where EVERY width is one), else any of its
+// widths, else tw (no second class).
+int decode_mixed_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, const int32_t* h_wh, uint8_t* d_rgb,
+                            const hoh_index* idx, uint64_t* d_status, hipStream_t s) {
+  MixedJob mj;
+  MixedDims& d = mj.d;
+  memset(&d, 0, sizeof(d));
+  d.n = n;
+  for (int i = 0; i < n; i++) {
+    d.wh[2 * i] = h_wh[2 * i]; d.wh[2 * i + 1] = h_wh[2 * i + 1];
+    d.wmax = std::max(d.wmax, d.wh[2 * i]);
+    d.hmax = std::max(d.hmax, d.wh[2 * i + 1]);
+  }
+  d.pitch = (d.wmax + 15) & ~15;
+  mj.dst = d_rgb;
+  int we = d.wmax;
+  for (int i = 0; i < n; i++) {
+    const int wi = d.wh[2 * i];
+    if (wi != d.wmax && (we == d.wmax || (we % 16 == 0 && wi % 16 != 0))) we = wi;
+  }
+  AsyncDec as;
+  as.hdr[0] = as.hdr[1] = 0;
+  as.hl = 0;                                      // k_dmixed checks the headers
+  as.status = d_status;
+  as.bytes = 0;
+  DecJob j;
+  memset(&j, 0, sizeof(j));
+  j.W = d.pitch; j.H = d.hmax * n;                // the staging surface (decode_run points j.rgb at it)
+  j.xt = 1; j.yt = n; j.tw = d.wmax; j.th = d.hmax;
+  j.we = we;
+  j.ntiles = n;
+  if (n > 1) { j.nimg = n; j.img_tiles = 1; j.in_stride = stride; }
+  j.in = d_in;
+  j.size = (uint64_t)n * stride;
+  return decode_run(c, j, idx, s, &as, nullptr, &mj);
+}
+
 // copies reading the row above that make an LZ tile a chain tile (knobs LZ_XROW, LZ_XROW_BATCH).
 // A batch decodes many images' LZ tiles at once, and there the raster chains (less work per tile
 // than the dynamic wavefront) pay from 2 such copies on: natural 8192^2 -s0 pipeline 50.1 -> 53.5
@@ -3401,9 +3454,11 @@ static uint32_t dl_budget() {
 static int dl_wg_per_cu() { return std::max(1, HOH_KNOB(DL_WG, 3)); }
 
 static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s, const AsyncDec* as,
-                      const RegionJob* rg) {
+                      const RegionJob* rg, const MixedJob* mx) {
   j.exp = (uint32_t)HOH_KNOB(EXP, 0);
-  if (!rg) j.we = j.W - (j.xt - 1) * j.tw;      // the edge column's width (a region job brings its files')
+  // the edge column's width (a region job brings its files', a mixed job a width that stands for
+  // its second class)
+  if (!rg && !mx) j.we = j.W - (j.xt - 1) * j.tw;
   j.npix_cap = (uint32_t)(((size_t)j.tw * j.th + 63) / 64 * 64);
   j.lz_cap = (uint32_t)((j.npix_cap / 4 + j.npix_cap / 255 + 16 + 7) / 8 * 8);
   {
@@ -3449,6 +3504,10 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     j.gid = rgid;
     j.file_tiles = a.file_tiles;
   }
+  // a mixed-shape batch: the staging surface of one pitch (a slab of hmax rows per file)
+  if (mx) {
+    if ((e = dbuf(w, 16, (size_t)mx->d.pitch * mx->d.hmax * nfiles * 3 + 16, &q))) return e; j.rgb = (uint8_t*)q;
+  }
   j.lz_xrow = lz_xrow(j.nimg > 1);
   if (index_nstreams(idx)) {                  // a batch's index serves that batch's layout only (an empty one: any)
     uint64_t st = 0;
@@ -3465,7 +3524,10 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   ctx_mark(c, s, "start", as == nullptr);
   const int nfile = j.nimg > 1 ? j.nimg : 1;
   if (as && as->hl) hipLaunchKernelGGL(k_dhdr, dim3(nfile), dim3(64), 0, s, j, as->hdr[0], as->hdr[1], as->hl);
-  if (rg) {
+  if (mx) {
+    // each file's header against its own shape, and its one tile's DecTile
+    launch_dmixed(mx->d, j.in, j.size, nfile > 1 ? j.in_stride : j.size, j.tiles, j.gerr, s);
+  } else if (rg) {
     // every tile's offset from the whole table (a prefix sum: read whole, one workgroup per file),
     // then the covered tiles' DecTile records and index numbers
     DecJob jt = j;
@@ -3552,14 +3614,19 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     j.lzband = br_few;
     // + the chain tiles' workgroups (ring R >= 2w: row 0 reads T / TL from the initial half values)
     const int we = j.we;                                                // the edge column's width
-    const int ga = (j.ntiles + CH_T - 1) / CH_T, gc = ga * (we != j.tw ? 2 : 1);
+    // (a mixed job's second class holds many widths: a workgroup per tile, k_dunpred_lz MIXED)
+    const int ga = (j.ntiles + CH_T - 1) / CH_T, gc = mx ? ga + (we != j.tw ? j.ntiles : 0) : ga * (we != j.tw ? 2 : 1);
     const bool r512 = 2 * j.tw <= 512;
     const size_t cl = r512 ? ch_smem(512) : ch_smem(1024);
     const int wf = std::min(j.ntiles, LZ_FEW), full1 = j.tw % 16 == 0, full2 = we % 16 == 0;
     auto launch = [&](int grid, size_t band, int br, int many) {
       const size_t l = std::max(band, cl);
-      if (r512) hipLaunchKernelGGL(k_dunpred_lz<512>, dim3(grid + gc), dim3(64), l, s, j, br, many, grid, ga, full1, full2);
-      else hipLaunchKernelGGL(k_dunpred_lz<1024>, dim3(grid + gc), dim3(64), l, s, j, br, many, grid, ga, full1, full2);
+      if (mx) {
+        if (r512) hipLaunchKernelGGL((k_dunpred_lz<512, true>), dim3(grid + gc), dim3(64), l, s, j, br, many, grid, ga, full1, full2);
+        else hipLaunchKernelGGL((k_dunpred_lz<1024, true>), dim3(grid + gc), dim3(64), l, s, j, br, many, grid, ga, full1, full2);
+      }
+      else if (r512) hipLaunchKernelGGL((k_dunpred_lz<512, false>), dim3(grid + gc), dim3(64), l, s, j, br, many, grid, ga, full1, full2);
+      else hipLaunchKernelGGL((k_dunpred_lz<1024, false>), dim3(grid + gc), dim3(64), l, s, j, br, many, grid, ga, full1, full2);
     };
     launch(wf, (size_t)(br_few + 1) * rowb, br_few, 0);
     // the wavefront workgroups stride over the LZ tile list, so more of them than the CUs hold
@@ -3576,9 +3643,14 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     launch_dcrop(rg->a, j.rgb, rg->dst, rg->pitch, j.gerr, s);
     ctx_mark(c, s, "dcrop", false);
   }
+  if (mx) {                                                            // the images, out of the staging surface
+    launch_mscatter(mx->d, j.rgb, mx->dst, j.gerr, s);
+    ctx_mark(c, s, "mscatter", false);
+  }
   if (hipGetLastError() != hipSuccess) return 3;
   if (as) {
-    launch_status_dec(j.gerr, as->bytes, as->status, s, j.nimg > 1 ? j.nimg : 1);
+    if (mx) launch_mstatus_dec(mx->d, j.gerr, as->status, s);          // a byte count per image
+    else launch_status_dec(j.gerr, as->bytes, as->status, s, j.nimg > 1 ? j.nimg : 1);
     return hipGetLastError() == hipSuccess ? 0 : 3;
   }
   uint64_t* pin = ctx_pinned(c);

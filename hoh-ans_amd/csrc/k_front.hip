@@ -84,17 +84,32 @@ __device__ __forceinline__ uint32_t px_mem(const uint8_t* img, size_t pitch, int
   return p[0] | (p[1] << 8) | (p[2] << 16);
 }
 
-template <bool RINGED, uint32_t RG>
-__device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring) {
+// A tile's rectangle: from the job's grid, or (MIXED: a mixed-shape batch, hoh_internal.h
+// MixedDims) its own w x h at the top left of slab t of the staging surface.  The variants are
+// instantiations of their own (k_front_mixed, k_colours_mixed): the kernels of the other entry
+// points compile as they did before.
+template <bool MIXED>
+__device__ __forceinline__ void tile_rect(const EncodeJob& j, const MixedDims* md, int t, int& x0, int& y0, int& w, int& h) {
+  if (MIXED) {
+    x0 = 0; y0 = t * j.th;
+    w = md->wh[2 * t]; h = md->wh[2 * t + 1];
+  } else {
+    const int gt = j.t0 + t;
+    x0 = (gt % j.xt) * j.tw; y0 = (gt / j.xt) * j.th;
+    w = min(j.tw, j.W - x0); h = min(j.th, j.H - y0);
+  }
+}
+
+template <bool RINGED, uint32_t RG, bool MIXED = false>
+__device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring, const MixedDims* md = nullptr) {
   __shared__ uint32_t wkey[4][WTAB + 1];
   __shared__ uint32_t wdup[4][WTAB / 32];
   __shared__ uint32_t hist[3 * 512 - 256];         // G: 256 bins at 0, R': 512 at 256, B': 512 at 768
   __shared__ int s_notgrey, s_ncand;
 
   const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int gt = j.t0 + t;
-  const int x0 = (gt % j.xt) * j.tw, y0 = (gt / j.xt) * j.th;
-  const int w = min(j.tw, j.W - x0), h = min(j.th, j.H - y0);
+  int x0, y0, w, h;
+  tile_rect<MIXED>(j, md, t, x0, y0, w, h);
   const uint32_t npix = (uint32_t)w * h;
   for (int i = tid; i < 3 * 512 - 256; i += NT) hist[i] = 0;
   for (int i = lane; i <= WTAB; i += 64) wkey[wv][i] = 0;
@@ -299,15 +314,15 @@ __device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring) {
 // palette in first-occurrence order (choh.cpp:64-88).  One workgroup per tile walks raster blocks
 // and stops as soon as a tile has shown 257 colours, which natural tiles do within a block or
 // two, so k_front carries no colour set (and fits seven workgroups per CU).
-__global__ __launch_bounds__(NT) void k_colours(EncodeJob j) {
+template <bool MIXED>
+__device__ __forceinline__ void colours_tile(const EncodeJob& j, const MixedDims* md) {
   __shared__ uint32_t hset[CSET];
   __shared__ uint32_t hpos[CSET];                   // first raster position of each colour
   __shared__ uint32_t pc[256], pp[256];
   __shared__ int s_ncol, s_np;
   const int t = blockIdx.x, tid = threadIdx.x;
-  const int gt = j.t0 + t;
-  const int x0 = (gt % j.xt) * j.tw, y0 = (gt / j.xt) * j.th;
-  const int w = min(j.tw, j.W - x0), h = min(j.th, j.H - y0);
+  int x0, y0, w, h;
+  tile_rect<MIXED>(j, md, t, x0, y0, w, h);
   const uint32_t npix = (uint32_t)w * h;
   const uint8_t* img = j.rgb + ((size_t)y0 * j.W + x0) * 3;
   const size_t pitch = (size_t)j.W * 3;
@@ -373,10 +388,19 @@ __global__ __launch_bounds__(NT) void k_colours(EncodeJob j) {
   if (tid == 0) j.ncol[t] = s_ncol;
 }
 
+__global__ __launch_bounds__(NT) void k_colours(EncodeJob j) { colours_tile<false>(j, nullptr); }
+__global__ __launch_bounds__(NT) void k_colours_mixed(EncodeJob j, MixedDims d) { colours_tile<true>(j, &d); }
+
 template <uint32_t RG>
 __global__ __launch_bounds__(NT) void k_front(EncodeJob j) {
   __shared__ uint32_t ring[2 * RG + 4];
   front_tile<true, RG>(j, ring);
+}
+
+template <uint32_t RG>
+__global__ __launch_bounds__(NT) void k_front_mixed(EncodeJob j, MixedDims d) {
+  __shared__ uint32_t ring[2 * RG + 4];
+  front_tile<true, RG, true>(j, ring, &d);
 }
 
 __global__ __launch_bounds__(NT) void k_front_wide(EncodeJob j) { front_tile<false, 1>(j, nullptr); }
@@ -905,4 +929,13 @@ void launch_front(const EncodeJob& j, hipStream_t s) {
   else if (j.tw <= RING_SMALL_MAX_W) hipLaunchKernelGGL(k_front<RING_SMALL>, dim3(j.ntiles), dim3(NT), 0, s, j);
   else if (j.tw <= RING_MAX_W) hipLaunchKernelGGL(k_front<RING>, dim3(j.ntiles), dim3(NT), 0, s, j);
   else hipLaunchKernelGGL(k_front_wide, dim3(j.ntiles), dim3(NT), 0, s, j);
+}
+
+// A mixed-shape batch: tiles of at most 511 x 511 with their own w, h (the ringed kernels, sized
+// by the widest).  Never k_front256, which takes w = h = 256 for every tile: a batch whose maxima
+// are exactly 256 x 256 holds smaller tiles too.
+void launch_front_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s) {
+  hipLaunchKernelGGL(k_colours_mixed, dim3(j.ntiles), dim3(NT), 0, s, j, d);
+  if (j.tw <= RING_SMALL_MAX_W) hipLaunchKernelGGL(k_front_mixed<RING_SMALL>, dim3(j.ntiles), dim3(NT), 0, s, j, d);
+  else hipLaunchKernelGGL(k_front_mixed<RING>, dim3(j.ntiles), dim3(NT), 0, s, j, d);
 }

@@ -8,6 +8,7 @@
 //             number in the side index's numbering (gid = file * file_tiles + tile).
 //  k_dcrop:   copies each window out of the staging surface to the caller's rows (any pitch).
 #include "hoh_dec.h"
+#include "hoh_rowmove.h"
 
 // Both kernels are bound by memory latency / bandwidth and tiny beside the decode: no LDS, no
 // barriers, one wave per unit of work.
@@ -47,10 +48,10 @@ __global__ __launch_bounds__(64) void k_dregion(RegionArgs a, const DecTile* tab
   }
 }
 
-// One wave per window row.  Source (staging) and destination agree mod 16 for many windows (both
-// pitches multiples of 16, x * 3 too): 16-byte moves between a byte head and tail.  Otherwise the
-// destination still gets aligned dword stores, each assembled from the two source dwords that hold
-// it (the staging surface ends in 16 spare bytes, so the second dword of a row's last one exists).
+// One wave per window row (wave_move_row, hoh_rowmove.h).  Source (staging) and destination agree
+// mod 16 for many windows (both pitches multiples of 16, x * 3 too): 16-byte moves between a byte
+// head and tail.  Otherwise the destination still gets aligned dword stores, each assembled from
+// the two source dwords that hold it.
 #define CROP_ROWS 4      // rows (waves) per workgroup
 __global__ __launch_bounds__(64 * CROP_ROWS) void k_dcrop(RegionArgs a, const uint8_t* stage, uint8_t* dst, size_t pitch,
                                                           const uint32_t* gerr) {
@@ -62,29 +63,7 @@ __global__ __launch_bounds__(64 * CROP_ROWS) void k_dcrop(RegionArgs a, const ui
   const int sx = x - (x / a.tw) * a.tw, sy = y - (y / a.th) * a.th;   // the window inside its cover
   const uint8_t* s = stage + (((size_t)f * a.sh + sy + r) * a.sw + sx) * 3;
   uint8_t* d = dst + ((size_t)f * a.h + r) * pitch;
-  const uint32_t nb = (uint32_t)a.w * 3;
-  const uint32_t wide = (((uintptr_t)s ^ (uintptr_t)d) & 15) == 0 ? 16u : 4u;
-  uint32_t head = (uint32_t)(-(intptr_t)d) & (wide - 1);      // bytes up to the destination's alignment
-  if (head > nb) head = nb;
-  const uint32_t body = (nb - head) / wide;                   // aligned units
-  const uint32_t tail0 = head + body * wide;
-  if ((uint32_t)lane < head) d[lane] = s[lane];
-  if ((uint32_t)lane < nb - tail0) d[tail0 + lane] = s[tail0 + lane];
-  if (wide == 16) {
-    const uint4* s4 = (const uint4*)(s + head);
-    uint4* d4 = (uint4*)(d + head);
-    for (uint32_t i = lane; i < body; i += 64) d4[i] = s4[i];
-  } else {
-    const uint8_t* sb = s + head;
-    const uint32_t sh = (uint32_t)((uintptr_t)sb & 3);
-    const uint32_t* sw = (const uint32_t*)(sb - sh);
-    uint32_t* d1 = (uint32_t*)(d + head);
-    if (sh == 0) {
-      for (uint32_t i = lane; i < body; i += 64) d1[i] = sw[i];
-    } else {
-      for (uint32_t i = lane; i < body; i += 64) d1[i] = __builtin_amdgcn_alignbyte(sw[i + 1], sw[i], sh);
-    }
-  }
+  wave_move_row(s, d, (uint32_t)a.w * 3, lane);
 }
 
 void launch_dregion(const RegionArgs& a, const DecTile* table, DecTile* tiles, uint32_t* gid, uint32_t* gerr,

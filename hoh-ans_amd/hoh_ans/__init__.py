@@ -96,6 +96,9 @@ def lib():
             ("hoh_decode_image_async", [vp, vp, sz, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
             ("hoh_encode_images_async", [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
             ("hoh_decode_images_async", [vp, C.c_int, vp, sz, C.c_int, C.c_int, vp, vp, vp, vp]),
+            ("hoh_mixed_rgb_bytes", [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+            ("hoh_encode_mixed_async", [vp, C.c_int, vp, C.POINTER(C.c_int32), C.c_int, vp, sz, vp, vp, vp]),
+            ("hoh_decode_mixed_async", [vp, C.c_int, vp, sz, C.POINTER(C.c_int32), vp, vp, vp, vp]),
             ("hoh_region_cover", [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
             ("hoh_decode_region", [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, sz, ip, ip, vp, vp]),
             ("hoh_decode_region_async", [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, sz,
@@ -133,6 +136,8 @@ def lib():
                 getattr(L, name).argtypes = args
         if hasattr(L, "hoh_index_serialized_size"):
             L.hoh_index_serialized_size.restype = sz
+        if hasattr(L, "hoh_mixed_rgb_bytes"):
+            L.hoh_mixed_rgb_bytes.restype = sz
         if hasattr(L, "hoh_entropy_bound"):
             L.hoh_entropy_bound.restype = sz
             L.hoh_entropy_bound.argtypes = [sz, sz, C.c_uint32]
@@ -407,6 +412,56 @@ def decode_images_async(hoh_dev, n, stride, W, H, out_dev, status_dev, ctx=None,
                                       _stream_ptr(torch, ctx))
     check(r, "hoh_decode_images_async")
     _after_call(torch, ctx)
+
+
+def _mixed_wh(shapes):
+    flat = [int(v) for p in shapes for v in p]
+    if len(flat) != 2 * len(shapes):
+        raise HohError(1, "mixed batch: shapes must be (W, H) pairs")
+    return (C.c_int32 * max(len(flat), 1))(*flat)
+
+
+def mixed_rgb_bytes(shapes):
+    """hoh_mixed_rgb_bytes: (total, offsets) of the packed layout of a mixed-shape batch -- image i of
+    shapes[i] = (W, H) lies at offsets[i] (len(shapes) + 1 entries, the last one the total).  Host
+    only.  HohError(E_ARG) when a shape is outside the small class or the count outside 1..256."""
+    n = len(shapes)
+    off = (C.c_uint64 * (max(n, 0) + 1))()
+    total = lib().hoh_mixed_rgb_bytes(n, _mixed_wh(shapes), off)
+    if total == 0:
+        raise HohError(1, "hoh_mixed_rgb_bytes")
+    return int(total), [int(v) for v in off]
+
+
+def encode_mixed_async(rgb_dev, shapes, out_dev, stride, status_dev, ctx=None, index=None, speed=0):
+    """Enqueue-only hoh_encode_mixed_async: len(shapes) small-class images of shapes[i] = (W, H),
+    packed back to back in rgb_dev (mixed_rgb_bytes), into files at out_dev + i*stride; status_dev:
+    int64 tensor of 2n ({code, size} per image).  At -s0 the batch is one job and `index` records its
+    side index; the context needs no option."""
+    import torch
+    ctx = ctx or default_ctx()
+    n = len(shapes)
+    assert out_dev.numel() >= n * stride and status_dev.numel() >= 2 * n
+    r = lib().hoh_encode_mixed_async(ctx.h, n, vp(rgb_dev.data_ptr()), _mixed_wh(shapes), speed,
+                                     vp(out_dev.data_ptr()), stride, index.h if index is not None else None,
+                                     vp(status_dev.data_ptr()), _stream_ptr(torch, ctx))
+    _after_call(torch, ctx)
+    check(r, "hoh_encode_mixed_async")
+
+
+def decode_mixed_async(hoh_dev, stride, shapes, out_dev, status_dev, ctx=None, index=None):
+    """Enqueue-only hoh_decode_mixed_async: the files at hoh_dev + i*stride, file i of shapes[i] =
+    (W, H), into the packed images of out_dev (mixed_rgb_bytes); status_dev: int64 tensor of 2n
+    ({code, W*H*3} per image)."""
+    import torch
+    ctx = ctx or default_ctx()
+    n = len(shapes)
+    assert hoh_dev.numel() >= n * stride and status_dev.numel() >= 2 * n
+    r = lib().hoh_decode_mixed_async(ctx.h, n, vp(hoh_dev.data_ptr()), stride, _mixed_wh(shapes),
+                                     vp(out_dev.data_ptr()), index.h if index is not None else None,
+                                     vp(status_dev.data_ptr()), _stream_ptr(torch, ctx))
+    _after_call(torch, ctx)
+    check(r, "hoh_decode_mixed_async")
 
 
 def region_cover(W, H, x, y, w, h):
@@ -695,6 +750,60 @@ def choh(rgb, ctx=None, speed=0, decodable=None, small=None):
             ctx.set_option(OPT_SMALL_IMAGES, was_small)
     torch.cuda.synchronize()
     return out[:n].cpu().numpy().tobytes(), printed
+
+
+def choh_mixed(images, ctx=None, speed=0, decodable=None):
+    """A list of (H, W, 3) uint8 arrays of the small class, any mix of shapes -> the list of their
+    .hoh files (header || tile, as choh(..., small=True) writes each), coded by one
+    hoh_encode_mixed_async call.  decodable as in choh."""
+    import torch
+    ctx = ctx or default_ctx()
+    imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+    shapes = [(a.shape[1], a.shape[0]) for a in imgs]
+    total, _ = mixed_rgb_bytes(shapes)
+    d = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).cuda()
+    stride = max(lib().hoh_encode_bound(w, h) for w, h in shapes)
+    out = torch.empty(len(imgs) * stride, dtype=torch.uint8, device="cuda")
+    st = torch.zeros(2 * len(imgs), dtype=torch.int64, device="cuda")
+    was = getattr(ctx, "decodable", 0)
+    if decodable is not None:
+        ctx.set_option(OPT_DECODABLE, 1 if decodable else 0)
+    try:
+        encode_mixed_async(d, shapes, out, stride, st, ctx=ctx, speed=speed)
+    finally:
+        if decodable is not None:
+            ctx.set_option(OPT_DECODABLE, was)
+    torch.cuda.synchronize()
+    sth = st.cpu().numpy()
+    outh = out.cpu().numpy()
+    files = []
+    for i in range(len(imgs)):
+        size = check_status(sth[2 * i:2 * i + 2], "hoh_encode_mixed_async[%d]" % i)
+        files.append(outh[i * stride:i * stride + size].tobytes())
+    return files
+
+
+def dhoh_mixed(files, shapes, ctx=None):
+    """The inverse of choh_mixed: a list of small-class .hoh files and their (W, H) -> the list of
+    (H, W, 3) arrays, decoded by one hoh_decode_mixed_async call."""
+    import torch
+    ctx = ctx or default_ctx()
+    shapes = [(int(w), int(h)) for w, h in shapes]
+    total, off = mixed_rgb_bytes(shapes)
+    stride = max(len(f) for f in files)
+    buf = np.zeros(len(files) * stride, np.uint8)
+    for i, f in enumerate(files):
+        buf[i * stride:i * stride + len(f)] = np.frombuffer(bytes(f), np.uint8)
+    b = torch.from_numpy(buf).cuda()
+    out = torch.empty(total, dtype=torch.uint8, device="cuda")
+    st = torch.zeros(2 * len(files), dtype=torch.int64, device="cuda")
+    decode_mixed_async(b, stride, shapes, out, st, ctx=ctx)
+    torch.cuda.synchronize()
+    sth = st.cpu().numpy()
+    for i in range(len(files)):
+        check_status(sth[2 * i:2 * i + 2], "hoh_decode_mixed_async[%d]" % i)
+    o = out.cpu().numpy()
+    return [o[off[i]:off[i + 1]].reshape(h, w, 3).copy() for i, (w, h) in enumerate(shapes)]
 
 
 def dhoh(data, ctx=None, index=None):

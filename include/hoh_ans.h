@@ -134,7 +134,8 @@ void hoh_reset_kernel_stats(hoh_ctx* ctx);
  * Untiled shapes OUTSIDE the small class (one side under 256, the other 512 or more) behave as at
  * 0 on every entry point: the decoder's LDS rows and rings are sized for tiles under 512 wide.
  * Not covered either way: hoh_decode_region* and hoh_region_cover (HOH_E_UNSUPPORTED for untiled
- * shapes), hoh_encode_tiles* / hoh_decode_tiles*, hoh_mgpu_*, batches of mixed shapes. */
+ * shapes), hoh_encode_tiles* / hoh_decode_tiles*, hoh_mgpu_*.  Batches of mixed shapes have calls of
+ * their own, hoh_encode_mixed_async / hoh_decode_mixed_async, which need no option. */
 #define HOH_OPT_SMALL_IMAGES 4
 int hoh_ctx_set_option(hoh_ctx* ctx, int option, int64_t value);
 
@@ -278,6 +279,45 @@ int hoh_encode_images_async(hoh_ctx* ctx, int n, const uint8_t* d_rgb, int W, in
                             size_t stride, hoh_index* idx, uint64_t* d_status, void* stream);
 int hoh_decode_images_async(hoh_ctx* ctx, int n, const uint8_t* d_hoh, size_t stride, int W, int H, uint8_t* d_rgb,
                             const hoh_index* idx, uint64_t* d_status, void* stream);
+
+/* ---- mixed-shape batches of small images ---------------------------------------------------
+ * n images of the small class (W <= 511 and H <= 511, see HOH_OPT_SMALL_IMAGES), each with its own
+ * shape, per call: a folder of thumbnails, crops or dataset samples without one call per image and
+ * without padding.  h_wh (host) holds W_0, H_0, W_1, H_1, ... and is read only during the call.  The
+ * images are packed back to back on both sides: image i is W_i*H_i*3 bytes at d_rgb + offsets[i]
+ * (hoh_mixed_rgb_bytes).  File i is written at / read from d_hoh + i*stride as in
+ * hoh_*_images_async; d_status holds 2n u64, {status, size} per image (decode: size = W_i*H_i*3).
+ * Both calls are enqueue-only and need no context option: they are new, and always write and read
+ * the small-class single-tile file, header || tile.  HOH_OPT_DECODABLE, HOH_OPT_NOIX_DECODER and
+ * HOH_OPT_CHAIN_TABLES apply as everywhere else.  File i is byte-identical to what hoh_encode_image
+ * writes for image i under HOH_OPT_SMALL_IMAGES at the same speed and options.
+ * Encode: at -s0 the whole batch is ONE job (the n images are the n tiles of a stack of Wmax x Hmax
+ * slabs on a staging surface in the context's workspace), and idx, if given, records the batch's
+ * side index: nimg = n, the batch's stride, serialising to the bytes of hoh_index_concat over the n
+ * single-image indexes.  At -s1..-s4 maximal runs of consecutive equal shapes run as uniform small
+ * stacks one after another (a run of one as a single image), and idx is emptied as in the other
+ * -s>=1 calls; between two runs the host waits for the stream, because the search's log2 tables are
+ * per pixel count and the host rebuilds them (as in any sequence of -s>=1 calls of changing shape).  An image's own failure (HOH_E_CAP past its stride, HOH_E_UNREPRODUCIBLE) marks only
+ * its slot.
+ * Decode: one job for every file kind the small-class decoder reads (decodable -s>=1 general tiles
+ * and RGB mode included), with the index, without it, and under every HOH_OPT_NOIX_DECODER choice.
+ * The caller gives every W and H; each file's header is checked on the device (a mismatch:
+ * HOH_E_CORRUPT) and every parse of file i stays inside [i*stride, (i+1)*stride).  An error in any
+ * file marks every slot and leaves the caller's d_rgb untouched.
+ * Returned at once: HOH_E_ARG for n outside 1..HOH_MIXED_MAX_BATCH, null pointers, a non-positive
+ * dimension, or a non-empty index recorded for another n or stride; HOH_E_UNSUPPORTED for a shape
+ * outside the small class; HOH_E_CAP (encode) for a stride under 10 bytes, the longest header.
+ * Workspaces are grow-only: a repeat call with the same n, Wmax and Hmax allocates nothing, in
+ * whatever order the shapes come.
+ * Not covered: mixed -s>=1 batches as one job, tiled shapes, hoh_mgpu_*. */
+#define HOH_MIXED_MAX_BATCH 256
+/* host only: offsets[i] = sum over k < i of 3*W_k*H_k (n+1 entries, may be NULL); returns offsets[n];
+ * 0 (offsets untouched) if any shape is outside the small class or n is out of range */
+size_t hoh_mixed_rgb_bytes(int n, const int32_t* h_wh, uint64_t* offsets);
+int hoh_encode_mixed_async(hoh_ctx* ctx, int n, const uint8_t* d_rgb, const int32_t* h_wh, int speed,
+                           uint8_t* d_out, size_t stride, hoh_index* idx, uint64_t* d_status, void* stream);
+int hoh_decode_mixed_async(hoh_ctx* ctx, int n, const uint8_t* d_hoh, size_t stride, const int32_t* h_wh,
+                           uint8_t* d_rgb, const hoh_index* idx, uint64_t* d_status, void* stream);
 
 /* ---- region decode: a crop of a .hoh by decoding only its tiles ----------------------------
  * The tiles of a .hoh share no state, so a pixel window needs only the tiles it touches.  The
