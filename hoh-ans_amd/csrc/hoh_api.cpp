@@ -60,6 +60,10 @@ struct hoh_index {
   // its index on the device only, so the copy is fetched when first asked for.
   std::vector<IndexStream> host;
   bool host_ok = true;
+  // A batch whose files carry DIFFERENT stream counts (a mixed batch with tiled images, an index
+  // joined from such files): file i's streams are [fstream[i], fstream[i + 1]).  Empty: nstreams /
+  // nimg each.
+  std::vector<uint32_t> fstream;
   Buf stage;                    // serialize: destination offsets, then the packed checkpoints
   int device = -1;              // device of the buffers (set when they are first reserved)
 };
@@ -82,6 +86,7 @@ struct hoh_ctx {
 #endif
   Buf idx8, fpb, pinfo, lg;     // -s>=1 workspaces (fpb: fingerprints, then the tile-major pixels)
   Buf mstage;                   // mixed-shape batches: the encoder's staging surface (k_mgather)
+  Buf mtab;                     //   and, with tiled images in the batch, the tile table (k_mtab)
   Buf lzs;                      // -s>=2: LZ posting lists (k_lzsort): sorted positions + ping-pong (then the sorted fingerprints) + ranks
   uint32_t lg_key[4] = {0, 0, 0, 0};
   uint64_t lg_off[4] = {0, 0, 0, 0};
@@ -203,7 +208,7 @@ static void freebuf(Buf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.n = 
 void hoh_ctx_destroy(hoh_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  Buf* all[] = {&c->dbg, &c->mstage, &c->idx8, &c->fpb, &c->lzs, &c->pinfo, &c->lg, &c->sym, &c->hist, &c->candbits, &c->matches, &c->lzspec, &c->pal, &c->streams, &c->tiles, &c->hdr,
+  Buf* all[] = {&c->dbg, &c->mstage, &c->mtab, &c->idx8, &c->fpb, &c->lzs, &c->pinfo, &c->lg, &c->sym, &c->hist, &c->candbits, &c->matches, &c->lzspec, &c->pal, &c->streams, &c->tiles, &c->hdr,
                 &c->tab_fast, &c->tab_gen, &c->slabs, &c->ckpt, &c->misc, &c->tsizes};
   for (Buf* b : all) freebuf(*b);
   for (Buf& b : c->scr.chunks) freebuf(b);
@@ -421,6 +426,12 @@ static int ensure_log2_tables(hoh_ctx* c, int W, int H, EncodeJob& j, hipStream_
   return HOH_OK;
 }
 
+// a mixed batch with tiled images: the tile table and the largest tile of the job
+struct MixedTabJob {
+  MixedTab tab;
+  int tw, th;
+};
+
 // d_status == nullptr: synchronous (the host waits and maps the status word).  Otherwise
 // enqueue-only: {status code, total bytes} are written to d_status by the stream.
 static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int t0, int ntiles,
@@ -428,7 +439,7 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
                              uint32_t* d_tile_sizes, uint64_t* total_out, hoh_index* idx,
                              hipStream_t s, int speed = 0, uint64_t* d_status = nullptr, int nimg = 1,
                              uint64_t out_stride = 0, int small_n = 0, const MixedDims* mx = nullptr,
-                             const uint8_t* mx_src = nullptr) {
+                             const uint8_t* mx_src = nullptr, const MixedTabJob* mt = nullptr) {
   const bool async = d_status != nullptr;
   int xt, yt, tw, th;
   hoh_tiling(W, H, &xt, &yt, &tw, &th);
@@ -438,6 +449,9 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
   // mx: a mixed-shape batch (-s0, small_n = its n >= 2).  d_rgb is the staging surface of pitch W =
   // wmax, one slab of hmax rows per image, filled here from the caller's packed images mx_src; tile
   // i's own w, h come from mx (launch_front_mixed), its header length too (launch_layout_mixed)
+  // mt: a mixed batch with tiled images (small_n = 0): the surface is packed vertically, W x the
+  // sum of the heights, and the job's ntiles tiles (tw x th at most) come from the tile table
+  if (mt) { xt = 1; yt = ntiles; tw = mt->tw; th = mt->th; }
   if (tw > HOH_MAX_TILE_W || (size_t)tw * th > (1u << 24)) return HOH_E_UNSUPPORTED;
   // -s>=1: k_search keeps a tile's 40-px predictor grid (HOH_MAPCAP cells) in LDS and writes a
   // row's residuals four per thread; tiles are < 512 on a side, so only untiled images (one side
@@ -571,7 +585,14 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
       hipMemsetAsync(j.candbits, 0, (size_t)ntiles * (j.npix_cap / 64) * 8, s) != hipSuccess) return HOH_E_HIP;
   if (hipMemsetAsync(c->misc.p, 0, 64 + (size_t)nimg * 16, s) != hipSuccess) return HOH_E_HIP;
   prof.mark("memset");
-  if (mx) {
+  if (mt) {
+    launch_mtab(*mx, mt->tab, s);
+    prof.mark("mtab");
+    launch_mgather_tab(mt->tab, mx_src, (uint8_t*)d_rgb, s);
+    prof.mark("mgather");
+    launch_mheader_tab(*mx, d_out, out_stride, s);
+    prof.mark("mheader");
+  } else if (mx) {
     launch_mgather(*mx, mx_src, (uint8_t*)d_rgb, s);
     prof.mark("mgather");
     launch_mheader(*mx, d_out, out_stride, s);
@@ -580,7 +601,8 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
   // knob ENC_STOP = k (measurement, -s0): the encode stops after stage k (1 front, 2 palette, 3 LZ
   // + nuke, 4 tables, 5 chains, 6 rANS generic + finalize, 7 layout + assembly); output invalid
   const int stop = HOH_KNOB(ENC_STOP, 0);
-  if (mx) launch_front_mixed(j, *mx, s);
+  if (mt) launch_front_mtab(j, mt->tab, s);
+  else if (mx) launch_front_mixed(j, *mx, s);
   else launch_front(j, s);
   prof.mark("front");
   if (stop != 1) launch_palette(j, s);
@@ -615,9 +637,11 @@ static int encode_tiles_impl(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int
     prof.mark("rans_enc_gen");
     prof.mark("finalize");
     if (!stop || stop > 6) {
-      if (mx) launch_layout_mixed(j, *mx, s);
+      if (mt) launch_layout_mtab(j, *mx, mt->tab, s);
+      else if (mx) launch_layout_mixed(j, *mx, s);
       else launch_layout(j, s);
-      launch_assemble(j, (int)S, s);
+      if (mt) launch_assemble_mtab(j, mt->tab, (int)S, s);
+      else launch_assemble(j, (int)S, s);
     }
     prof.mark("layout");
     prof.mark("assemble");
@@ -892,10 +916,13 @@ int hoh_encode_images_async(hoh_ctx* c, int n, const uint8_t* d_rgb, int W, int 
   return HOH_OK;
 }
 
+// the shapes the mixed calls take: the small class and every tiled shape (hoh_tiling)
+static int mixed_shape(int W, int H) { return small_class(W, H) || tiled_shape(W, H); }
+
 size_t hoh_mixed_rgb_bytes(int n, const int32_t* h_wh, uint64_t* offsets) {
   if (n < 1 || n > HOH_MIXED_MAX_BATCH || !h_wh) return 0;
   for (int i = 0; i < n; i++)
-    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1])) return 0;
+    if (h_wh[2 * i] <= 0 || h_wh[2 * i + 1] <= 0 || !mixed_shape(h_wh[2 * i], h_wh[2 * i + 1])) return 0;
   uint64_t run = 0;
   for (int i = 0; i < n; i++) {
     if (offsets) offsets[i] = run;
@@ -905,11 +932,15 @@ size_t hoh_mixed_rgb_bytes(int n, const int32_t* h_wh, uint64_t* offsets) {
   return (size_t)run;
 }
 
-// n small-class images of n shapes, packed back to back.  -s0: ONE job -- the n images are the n
-// tiles of an xt = 1, yt = n stack of wmax x hmax slabs on a staging surface (k_mgather fills it),
-// tile i with its own w, h and its own header (MixedDims; k_front_mixed, k_layout_mixed).
-// -s1..-s4: the search keeps at most four log2 tables per job (EncodeJob::lg_n), so maximal runs of
-// consecutive equal shapes go through the uniform small stack (encode_small_batch) one after another.
+// n images of n shapes, packed back to back.  All of the small class, -s0: ONE job -- the n images
+// are the n tiles of an xt = 1, yt = n stack of wmax x hmax slabs on a staging surface (k_mgather
+// fills it), tile i with its own w, h and its own header (MixedDims; k_front_mixed, k_layout_mixed).
+// With tiled images among them, -s0: ONE job too -- the surface is packed vertically (pitch Wmax,
+// image i on rows [Y_i, Y_i + H_i)) and the job's tiles, a different number per file, come from a
+// tile table on the device (MixedTab; k_mtab, k_front_mtab, k_layout_mtab, k_tilebytes_mtab).
+// -s1..-s4: the search keeps at most four log2 tables per job (EncodeJob::lg_n; one tiled shape
+// uses up to four by itself), so maximal runs of consecutive equal shapes go through the uniform
+// batches (encode_small_batch, hoh_encode_images_async) one after another.
 int hoh_encode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_rgb, const int32_t* h_wh, int speed, uint8_t* d_out,
                            size_t stride, hoh_index* idx, uint64_t* d_status, void* stream) {
   if (!c || n < 1 || n > HOH_MIXED_MAX_BATCH || !d_rgb || !h_wh || !d_out || !d_status || speed < 0 || speed > 4 ||
@@ -917,9 +948,12 @@ int hoh_encode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_rgb, const int32_
     return HOH_E_ARG;
   for (int i = 0; i < n; i++)
     if (h_wh[2 * i] <= 0 || h_wh[2 * i + 1] <= 0) return HOH_E_ARG;
-  for (int i = 0; i < n; i++)
-    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1])) return HOH_E_UNSUPPORTED;
-  if (stride < 10) return HOH_E_CAP;                  // the longest header of the class
+  bool tiled = false;
+  for (int i = 0; i < n; i++) {
+    if (!mixed_shape(h_wh[2 * i], h_wh[2 * i + 1])) return HOH_E_UNSUPPORTED;
+    tiled |= tiled_shape(h_wh[2 * i], h_wh[2 * i + 1]) != 0;
+  }
+  if (stride < 10) return HOH_E_CAP;                  // the longest header of the small class
   (void)hipSetDevice(c->device);
   hipStream_t s = pick(c, stream);
   if (speed && idx) index_clear(idx);                 // -s>=1 files get no side index
@@ -929,8 +963,11 @@ int hoh_encode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_rgb, const int32_
       const int W = h_wh[2 * i], H = h_wh[2 * i + 1];
       int k = 1;
       while (i + k < n && h_wh[2 * (i + k)] == W && h_wh[2 * (i + k) + 1] == H) k++;
-      const int r = encode_small_batch(c, k, d_rgb + off, W, H, speed, d_out + (size_t)i * stride, stride,
-                                       speed ? nullptr : idx, d_status + 2 * i, s);
+      const int r = tiled_shape(W, H)
+                        ? hoh_encode_images_async(c, k, d_rgb + off, W, H, speed, d_out + (size_t)i * stride, stride,
+                                                  speed ? nullptr : idx, d_status + 2 * i, stream)
+                        : encode_small_batch(c, k, d_rgb + off, W, H, speed, d_out + (size_t)i * stride, stride,
+                                             speed ? nullptr : idx, d_status + 2 * i, s);
       if (r) return r;
       off += (size_t)k * W * H * 3;
       i += k;
@@ -946,11 +983,41 @@ int hoh_encode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_rgb, const int32_
     d.hmax = std::max(d.hmax, d.wh[2 * i + 1]);
   }
   d.pitch = d.wmax;
-  int e = ensure(c->mstage, (size_t)d.pitch * d.hmax * n * 3 + 16);
-  if (e) return e;
   uint64_t total = 0;
-  return encode_tiles_impl(c, (const uint8_t*)c->mstage.p, d.pitch, d.hmax * n, 0, n, d_out, stride, 0, 1, nullptr, &total,
-                           idx, s, 0, d_status, n, stride, n, &d, d_rgb);
+  if (!tiled) {
+    int e = ensure(c->mstage, (size_t)d.pitch * d.hmax * n * 3 + 16);
+    if (e) return e;
+    return encode_tiles_impl(c, (const uint8_t*)c->mstage.p, d.pitch, d.hmax * n, 0, n, d_out, stride, 0, 1, nullptr,
+                             &total, idx, s, 0, d_status, n, stride, n, &d, d_rgb);
+  }
+  // the job's tiles: their number, the largest, and each file's first stream for the side index
+  MixedTabJob mt;
+  mt.tw = mt.th = 0;
+  int64_t rows = 0, ntiles = 0;
+  std::vector<uint32_t> fs((size_t)n + 1);
+  bool equal = true;
+  for (int i = 0; i < n; i++) {
+    int xt, yt, tw, th;
+    mixed_tiling(d.wh[2 * i], d.wh[2 * i + 1], xt, yt, tw, th);
+    mt.tw = std::max(mt.tw, tw);
+    mt.th = std::max(mt.th, th);
+    fs[i] = (uint32_t)(ntiles * SK_PER_TILE);
+    rows += d.wh[2 * i + 1];
+    ntiles += (int64_t)xt * yt;
+    equal &= (int64_t)xt * yt * (i + 1) == ntiles;
+  }
+  if (rows > (1ll << 30) || ntiles > (1 << 24)) return HOH_E_ARG;
+  // the -s0 chains' 32-bit table bound (encode_tiles_impl), before anything is allocated for the job
+  if ((uint64_t)ntiles * SK_PER_TILE * HOH_FAST_STRIDE * sizeof(EncFast) > 0xffffffffull) return HOH_E_UNSUPPORTED;
+  fs[n] = (uint32_t)(ntiles * SK_PER_TILE);
+  int e = ensure(c->mstage, (size_t)d.pitch * (size_t)rows * 3 + 16);
+  if (e) return e;
+  if ((e = ensure(c->mtab, mixed_tab_bytes(n, (int)ntiles)))) return e;
+  mt.tab = mixed_tab_at(c->mtab.p, n, (int)ntiles, d.pitch, (int)rows);
+  const int r = encode_tiles_impl(c, (const uint8_t*)c->mstage.p, d.pitch, (int)rows, 0, (int)ntiles, d_out, stride, 0, 1,
+                                  nullptr, &total, idx, s, 0, d_status, n, stride, 0, &d, d_rgb, &mt);
+  if (r == HOH_OK && idx && !equal) idx->fstream.swap(fs);
+  return r;
 }
 
 int hoh_encode_image(hoh_ctx* c, const uint8_t* d_rgb, int W, int H, int speed, uint8_t* d_out, size_t cap,
@@ -1183,7 +1250,7 @@ static uint64_t canon_offsets(const std::vector<IndexStream>& h, uint64_t base, 
 extern "C" {
 
 size_t hoh_index_serialized_size(const hoh_index* idx) {
-  if (!idx || index_host(idx, nullptr) != HOH_OK) return 0;
+  if (!idx || !idx->fstream.empty() || index_host(idx, nullptr) != HOH_OK) return 0;
   uint64_t nck = 0;
   for (const IndexStream& x : idx->host) nck += rec_nseg(x);
   return HOH_BLOB_HDR + idx->host.size() * HOH_BLOB_REC + (size_t)nck * HOH_BLOB_CK;
@@ -1191,6 +1258,9 @@ size_t hoh_index_serialized_size(const hoh_index* idx) {
 
 int hoh_index_serialize(const hoh_index* cidx, uint8_t* out, size_t cap, size_t* written, void* stream) {
   if (!cidx || !written || (!out && cap)) return HOH_E_ARG;
+  // the version-1 blob has one stream count for all files: a batch of unequal files is persisted
+  // file by file (hoh_index_file) and put together again with hoh_index_join
+  if (!cidx->fstream.empty()) return HOH_E_UNSUPPORTED;
   hoh_index* idx = const_cast<hoh_index*>(cidx);
   hipStream_t s = (hipStream_t)stream;
   int e;
@@ -1279,27 +1349,43 @@ int hoh_index_deserialize(hoh_index* idx, const uint8_t* blob, size_t size, void
   return HOH_OK;
 }
 
-int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream) {
+// dst = the index of n files at i * stride from their n single-file indexes.  equal: the stream
+// counts must agree (hoh_index_concat); otherwise any multiples of 7 (hoh_index_join), and dst
+// remembers each file's first stream when they differ.
+static int index_join_impl(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream, bool equal) {
   if (!dst || n <= 0 || !src) return HOH_E_ARG;
-  for (int i = 0; i < n; i++)
-    if (!src[i] || src[i] == dst || src[i]->nstreams != src[0]->nstreams || (src[i]->nstreams && src[i]->nimg != 1))
-      return HOH_E_ARG;
+  size_t total = 0;
+  bool same = true;
+  for (int i = 0; i < n; i++) {
+    if (!src[i] || src[i] == dst || (src[i]->nstreams && src[i]->nimg != 1)) return HOH_E_ARG;
+    if (equal ? src[i]->nstreams != src[0]->nstreams : src[i]->nstreams % SK_PER_TILE != 0) return HOH_E_ARG;
+    same &= src[i]->nstreams == src[0]->nstreams;
+    total += (size_t)src[i]->nstreams;
+  }
+  // (an empty source among non-empty ones describes no file: the decoder would take the joined
+  // index for the batch's and find its stream count wrong)
+  if (!same)
+    for (int i = 0; i < n; i++)
+      if (!src[i]->nstreams) return HOH_E_ARG;
   if (n > 1 && stride == 0) return HOH_E_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const size_t S = (size_t)src[0]->nstreams;
-  if (S * (size_t)n > 0x7fffffffull) return HOH_E_ARG;
+  if (total > 0x7fffffffull) return HOH_E_ARG;
   index_clear(dst);
-  if (!S) return HOH_OK;
+  if (!total) return HOH_OK;
   int e;
   for (int i = 0; i < n; i++)
     if ((e = index_host(src[i], s))) return e;
   if (src[0]->device >= 0) (void)hipSetDevice(src[0]->device);
   if (!s && hipDeviceSynchronize() != hipSuccess) return HOH_E_HIP;
-  std::vector<IndexStream> hs(S * n);
-  std::vector<uint32_t> off(S * n);
+  std::vector<IndexStream> hs(total);
+  std::vector<uint32_t> off(total);
+  std::vector<uint32_t> fs((size_t)n + 1);
   uint64_t run = 0;
+  size_t b = 0;
   for (int i = 0; i < n; i++) {
-    run = canon_offsets(src[i]->host, run, off.data() + S * i);
+    const size_t S = (size_t)src[i]->nstreams;
+    fs[i] = (uint32_t)b;
+    run = canon_offsets(src[i]->host, run, off.data() + b);
     for (size_t k = 0; k < S; k++) {
       const IndexStream& a = src[i]->host[k];
       IndexStream x;
@@ -1309,18 +1395,20 @@ int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_
         x.payload_off = a.payload_off + (uint64_t)i * (n > 1 ? stride : 0);
         x.n = a.n;
         x.words = a.words;
-        x.ckpt_off = off[S * i + k];
+        x.ckpt_off = off[b + k];
       }
-      hs[S * i + k] = x;
+      hs[b + k] = x;
     }
+    b += S;
   }
+  fs[n] = (uint32_t)b;
   if (run > 0xffffffffull) return HOH_E_ARG;
   if ((e = index_reserve(dst, hs.size(), (size_t)run))) return e;
   if ((e = ensure(dst->stage, off.size() * 4))) return e;
   if (hipMemcpyAsync(dst->stage.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) return HOH_E_HIP;
   for (int i = 0; i < n; i++)
     launch_index_pack((const IndexStream*)src[i]->streams.p, (const Checkpoint*)src[i]->ck.p,
-                      (const uint32_t*)dst->stage.p + S * i, (int)S, dst->ck.p, 0, s);
+                      (const uint32_t*)dst->stage.p + fs[i], src[i]->nstreams, dst->ck.p, 0, s);
   if (hipGetLastError() != hipSuccess) return HOH_E_HIP;
   if (hipMemcpyAsync(dst->streams.p, hs.data(), hs.size() * sizeof(IndexStream), hipMemcpyHostToDevice, s) != hipSuccess)
     return HOH_E_HIP;
@@ -1329,6 +1417,63 @@ int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_
   dst->ck_count = (size_t)run;
   dst->nimg = n;
   dst->stride = n > 1 ? stride : 0;
+  dst->host.swap(hs);
+  dst->host_ok = true;
+  if (!same) dst->fstream.swap(fs);
+  return HOH_OK;
+}
+
+int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream) {
+  return index_join_impl(dst, n, src, stride, stream, true);
+}
+
+int hoh_index_join(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream) {
+  return index_join_impl(dst, n, src, stride, stream, false);
+}
+
+// file i's own index out of a batch's: its streams, their payload offsets rebased to the file's
+// start, its checkpoints in the compact layout
+int hoh_index_file(const hoh_index* batch, int i, hoh_index* dst, void* stream) {
+  if (!batch || !dst || batch == dst || i < 0 || (batch->nstreams && i >= batch->nimg)) return HOH_E_ARG;
+  index_clear(dst);
+  if (!batch->nstreams) return HOH_OK;                        // an empty index: every file's is empty
+  hipStream_t s = (hipStream_t)stream;
+  int e;
+  if ((e = index_host(batch, s))) return e;
+  if (batch->device >= 0) (void)hipSetDevice(batch->device);
+  if (!s && hipDeviceSynchronize() != hipSuccess) return HOH_E_HIP;
+  const size_t per = (size_t)batch->nstreams / (size_t)batch->nimg;
+  const size_t a = batch->fstream.empty() ? per * i : batch->fstream[i];
+  const size_t S = (batch->fstream.empty() ? per * (i + 1) : batch->fstream[i + 1]) - a;
+  const uint64_t base = batch->nimg > 1 ? (uint64_t)i * batch->stride : 0;
+  std::vector<IndexStream> src(batch->host.begin() + a, batch->host.begin() + a + S);
+  std::vector<IndexStream> hs(S);
+  std::vector<uint32_t> off(S);
+  const uint64_t run = canon_offsets(src, 0, off.data());
+  for (size_t k = 0; k < S; k++) {
+    IndexStream x;
+    memset(&x, 0, sizeof(x));
+    x.mode = src[k].mode;
+    if (x.mode == SM_RANS) {
+      if (src[k].payload_off < base) return HOH_E_ARG;
+      x.payload_off = src[k].payload_off - base;
+      x.n = src[k].n;
+      x.words = src[k].words;
+      x.ckpt_off = off[k];
+    }
+    hs[k] = x;
+  }
+  if ((e = index_reserve(dst, S, (size_t)run))) return e;
+  if ((e = ensure(dst->stage, S * 4))) return e;
+  if (hipMemcpyAsync(dst->stage.p, off.data(), S * 4, hipMemcpyHostToDevice, s) != hipSuccess) return HOH_E_HIP;
+  launch_index_pack((const IndexStream*)batch->streams.p + a, (const Checkpoint*)batch->ck.p, (const uint32_t*)dst->stage.p,
+                    (int)S, dst->ck.p, 0, s);
+  if (hipGetLastError() != hipSuccess) return HOH_E_HIP;
+  if (hipMemcpyAsync(dst->streams.p, hs.data(), S * sizeof(IndexStream), hipMemcpyHostToDevice, s) != hipSuccess)
+    return HOH_E_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return HOH_E_HIP;
+  dst->nstreams = (int)S;
+  dst->ck_count = (size_t)run;
   dst->host.swap(hs);
   dst->host_ok = true;
   return HOH_OK;
@@ -1355,6 +1500,7 @@ void index_clear(hoh_index* idx) {
   idx->stride = 0;
   idx->host.clear();
   idx->host_ok = true;
+  idx->fstream.clear();
 }
 
 IndexStream* index_stream_buf(hoh_index* idx) { return (IndexStream*)idx->streams.p; }
@@ -1365,6 +1511,7 @@ int index_commit(hoh_index* idx, int nstreams, size_t nck, hipStream_t s) {
   idx->nimg = 1;
   idx->stride = 0;
   idx->host_ok = false;
+  idx->fstream.clear();
   return index_host(idx, s);
 }
 
@@ -1390,6 +1537,7 @@ int index_capture(hoh_index* idx, const EncodeJob& j, hipStream_t s) {
   idx->stride = j.nimg > 1 ? j.out_stride : 0;
   idx->host.clear();                        // the records exist on the device only (index_host)
   idx->host_ok = false;
+  idx->fstream.clear();
   launch_index_capture(j, (IndexStream*)idx->streams.p, per, s);
   return hipGetLastError() == hipSuccess ? HOH_OK : HOH_E_HIP;
 }

@@ -51,7 +51,8 @@ struct GenTile {
   GenLayer L[3];
 };
 
-#define HOH_DEC_NBUF 20      // slots 16..18: a region decode's staging surface, whole-file tile table and gid
+#define HOH_DEC_NBUF 20      // slots 16..18: a region decode's staging surface, whole-file tile table and gid;
+                             //   19: a mixed batch's tile table (MixedTab)
                              //   (16 is a mixed-shape batch's staging surface too)
 struct DecWork {
   void* bufs[HOH_DEC_NBUF] = {nullptr};
@@ -98,6 +99,10 @@ struct RegionJob {                  // what decode_run needs beside the DecJob o
 struct MixedJob {
   MixedDims d;
   uint8_t* dst;                     // the caller's packed images
+  // a batch with tiled images: files of different tile counts on a vertically packed surface
+  // (k_mtab's tile table; k_dtable_mtab is the front, k_dparse_file the parse)
+  int tiled;
+  int rows;                         //   surface rows: the sum of the heights
 };
 void launch_dmixed(const MixedDims& d, const uint8_t* in, uint64_t size, uint64_t stride, DecTile* tiles,
                    uint32_t* gerr, hipStream_t s);

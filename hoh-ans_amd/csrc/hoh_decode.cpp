@@ -157,7 +157,7 @@ int hoh_decode_mixed_async(hoh_ctx* c, int n, const uint8_t* d_hoh, size_t strid
   for (int i = 0; i < n; i++)
     if (h_wh[2 * i] <= 0 || h_wh[2 * i + 1] <= 0) return HOH_E_ARG;
   for (int i = 0; i < n; i++)
-    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1])) return HOH_E_UNSUPPORTED;
+    if (!small_class(h_wh[2 * i], h_wh[2 * i + 1]) && !tiled_shape(h_wh[2 * i], h_wh[2 * i + 1])) return HOH_E_UNSUPPORTED;
   (void)hipSetDevice(ctx_device(c));
   return decode_mixed_async_impl(c, n, d_hoh, stride, h_wh, d_rgb, idx, d_status, ctx_stream(c, stream));
 }

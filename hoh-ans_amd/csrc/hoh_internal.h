@@ -281,6 +281,9 @@ inline int batch_stacks(int W, int H) { return (W >= 512 || H >= 512) && W >= 25
 // Every device size derived from the tile width (LDS rows, rings, bands) holds up to 511.
 inline int small_class(int W, int H) { return W > 0 && H > 0 && W <= 511 && H <= 511; }
 
+// the shapes hoh_tiling tiles (choh.cpp:454-461); with the small class, the shapes the mixed calls take
+inline int tiled_shape(int W, int H) { return (W >= 512 || H >= 512) && W >= 256 && H >= 256; }
+
 // the image of tile t and the base of its file in out
 __host__ __device__ inline int tile_img(const EncodeJob& j, int t) { return j.nimg > 1 ? t / j.img_tiles : 0; }
 // a batch image's file is written only when it fits its stride and none of its tiles failed
@@ -364,6 +367,66 @@ __host__ __device__ inline uint32_t mixed_hdr_bytes(const MixedDims& d, int i, u
   uint32_t p = hoh_write_varint(o, 6, (uint64_t)d.wh[2 * i] - 1);
   return hoh_write_varint(o, p, (uint64_t)d.wh[2 * i + 1] - 1);
 }
+// A mixed batch that holds tiled images (any side of 512 or more): the files carry different
+// numbers of tiles, so the job's tiles come from a table on the device (k_mtab, from the dims passed
+// by value).  The staging surface is packed vertically: one pitch, image i on rows [y[i], y[i + 1]),
+// its tile (tx, ty) at x0 = tx * tw_i, y0 = y[i] + ty * th_i.
+struct MixedTile {
+  int32_t img;                        // the tile's image (= its file)
+  int32_t k;                          // its number inside its file
+  int32_t x0, y0, w, h;               // its rectangle on the staging surface
+};
+struct MixedTab {                     // passed to kernels by value; the arrays are device memory
+  MixedTile* tile;                    // [ntiles] job tile t
+  uint32_t* tfile;                    // [ntiles] tile t's file again, as the decoder's parse reads it (DecJob::gid)
+  int32_t* first;                     // [n + 1] file i's first job tile T_i; first[n] = ntiles
+  int32_t* y;                         // [n + 1] image i's first surface row Y_i; y[n] = the surface's rows
+  uint64_t* off;                      // [n + 1] image i's byte offset in the caller's packed buffer
+  uint64_t* ttotal;                   // [ntiles] encoder: the size of tile t's file and its files' TF_* flags, copied
+  uint32_t* terr;                     //   per tile for k_streambytes (k_tilebytes_mtab)
+  int32_t n, ntiles;
+  int32_t pitch;                      // surface pixels per row
+  int32_t rows;                       // surface rows: the sum of the heights
+};
+inline size_t mixed_tab_bytes(int n, int ntiles) {
+  return (size_t)ntiles * (sizeof(MixedTile) + 16) + (size_t)(n + 1) * 16 + 64;
+}
+inline MixedTab mixed_tab_at(void* p, int n, int ntiles, int pitch, int rows) {
+  MixedTab t;
+  t.off = (uint64_t*)p;
+  t.ttotal = t.off + n + 1;
+  t.tile = (MixedTile*)(t.ttotal + ntiles);
+  t.tfile = (uint32_t*)(t.tile + ntiles);
+  t.terr = t.tfile + ntiles;
+  t.first = (int32_t*)(t.terr + ntiles);
+  t.y = t.first + n + 1;
+  t.n = n; t.ntiles = ntiles; t.pitch = pitch; t.rows = rows;
+  return t;
+}
+// the tiling of image i (hoh_tiling): 1 x 1 for the small class
+__host__ __device__ inline void mixed_tiling(int W, int H, int& xt, int& yt, int& tw, int& th) {
+  if ((W >= 512 || H >= 512) && W >= 256 && H >= 256) {
+    xt = W / 256; yt = H / 256;
+    tw = (W + xt - 1) / xt; th = (H + yt - 1) / yt;
+  } else {
+    xt = yt = 1; tw = W; th = H;
+  }
+}
+// file i's bytes before its tile size table: the header, then the tiling bytes of a tiled image
+__host__ __device__ inline uint32_t mixed_prefix_bytes(const MixedDims& d, int i, uint8_t* o) {
+  uint32_t p = mixed_hdr_bytes(d, i, o);
+  int xt, yt, tw, th;
+  mixed_tiling(d.wh[2 * i], d.wh[2 * i + 1], xt, yt, tw, th);
+  if (xt * yt > 1) { o[p++] = (uint8_t)(xt - 1); o[p++] = (uint8_t)(yt - 1); }
+  return p;
+}
+void launch_mtab(const MixedDims& d, const MixedTab& tab, hipStream_t s);
+void launch_front_mtab(const EncodeJob& j, const MixedTab& tab, hipStream_t s);
+void launch_layout_mtab(const EncodeJob& j, const MixedDims& d, const MixedTab& tab, hipStream_t s);
+void launch_assemble_mtab(const EncodeJob& j, const MixedTab& tab, int nstreams, hipStream_t s);
+void launch_mgather_tab(const MixedTab& tab, const uint8_t* packed, uint8_t* stage, hipStream_t s);
+void launch_mheader_tab(const MixedDims& d, uint8_t* out, uint64_t stride, hipStream_t s);
+void launch_mscatter_tab(const MixedTab& tab, const uint8_t* stage, uint8_t* packed, const uint32_t* gerr, hipStream_t s);
 void launch_front_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s);
 void launch_layout_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s);
 void launch_mgather(const MixedDims& d, const uint8_t* packed, uint8_t* stage, hipStream_t s);

@@ -45,15 +45,18 @@ __device__ uint64_t block_excl_scan(uint64_t v, uint64_t* part, int tid) {
 // One workgroup per file: blockIdx.x = the image of a batch (its tiles [tb, te), its file at
 // img * out_stride), else the one file / shard blob.  MIXED (a mixed-shape batch, k_layout_mixed):
 // the bytes before the tiles are file img's own header, 8 to 10 bytes, instead of j.prefix; an
-// instantiation of its own, so k_layout compiles as before.
-template <bool MIXED>
-__device__ __forceinline__ void layout_file(const EncodeJob& j, const MixedDims* md) {
+// instantiation of its own, so k_layout compiles as before.  MIXED 2 (a mixed batch with tiled
+// images, k_layout_mtab): file img's tiles are [T_img, T_img+1) of the tile table, and a tiled
+// image's two tiling bytes follow its header.
+template <int MIXED>
+__device__ __forceinline__ void layout_file(const EncodeJob& j, const MixedDims* md, const int32_t* tfirst = nullptr) {
   __shared__ uint64_t part[1024];
   __shared__ uint64_t tot_size, tot_vlen;
   const int tid = threadIdx.x, img = blockIdx.x;
-  const int tb = j.nimg > 1 ? img * j.img_tiles : 0, te = j.nimg > 1 ? tb + j.img_tiles : j.ntiles;
+  const int tb = MIXED == 2 ? tfirst[img] : j.nimg > 1 ? img * j.img_tiles : 0;
+  const int te = MIXED == 2 ? tfirst[img + 1] : j.nimg > 1 ? tb + j.img_tiles : j.ntiles;
   const uint64_t fbase = j.nimg > 1 ? (uint64_t)img * j.out_stride : 0;
-  const uint64_t prefix = MIXED ? (uint64_t)mixed_hdr_len(*md, img) : j.prefix;
+  const uint64_t prefix = MIXED ? (uint64_t)mixed_hdr_len(*md, img) + (MIXED == 2 && te - tb > 1 ? 2 : 0) : j.prefix;
   if (tid == 0) { tot_size = 0; tot_vlen = 0; }
   __syncthreads();
   // pass 1: tile sizes and the table length
@@ -139,20 +142,42 @@ __device__ __forceinline__ void layout_file(const EncodeJob& j, const MixedDims*
   }
 }
 
-__global__ __launch_bounds__(1024) void k_layout(EncodeJob j) { layout_file<false>(j, nullptr); }
-__global__ __launch_bounds__(1024) void k_layout_mixed(EncodeJob j, MixedDims d) { layout_file<true>(j, &d); }
+__global__ __launch_bounds__(1024) void k_layout(EncodeJob j) { layout_file<0>(j, nullptr); }
+__global__ __launch_bounds__(1024) void k_layout_mixed(EncodeJob j, MixedDims d) { layout_file<1>(j, &d); }
+__global__ __launch_bounds__(1024) void k_layout_mtab(EncodeJob j, MixedDims d, const int32_t* first) {
+  layout_file<2>(j, &d, first);
+}
 
-__global__ __launch_bounds__(64) void k_tilebytes(EncodeJob j) {
+// MTAB (a mixed batch with tiled images, k_tilebytes_mtab: an instantiation of its own): a tile's
+// image and whether it is its file's last come from the tile table, not from t / img_tiles.  It also
+// copies its file's size and flags into per-TILE arrays (MixedTab::ttotal, terr): k_streambytes then
+// runs unchanged on a job whose "images" are the tiles (img_tiles = 1), so file_ok finds a stream's
+// file through its tile.
+template <bool MTAB>
+__device__ __forceinline__ bool file_ok_t(const EncodeJob& j, int t, const MixedTile* mt) {
+  if (!MTAB) return file_ok(j, t);
+  if (*j.gerr) return false;
+  const int img = mt[t].img;
+  return j.img_total[img] <= j.out_stride && !j.img_err[img];
+}
+
+template <bool MTAB>
+__device__ __forceinline__ void tilebytes(const EncodeJob& j, const MixedTile* mt, const int32_t* first,
+                                          uint64_t* ttotal, uint32_t* terr) {
   const int t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= j.ntiles || !file_ok(j, t)) return;
+  if (MTAB && t < j.ntiles) {
+    ttotal[t] = j.img_total[mt[t].img];
+    terr[t] = j.img_err[mt[t].img];
+  }
+  if (t >= j.ntiles || !file_ok_t<MTAB>(j, t, mt)) return;
   const TileInfo ti = j.tiles[t];
   const StreamInfo* st = j.streams + (size_t)t * j.spt;
   uint8_t* o = j.out + ti.off;
   o[0] = 0; o[1] = 0;                                  // 1x1 inner tiling (choh.cpp:115-116)
   o[2] = (uint8_t)ti.mode;                             // internal colour mode (:328)
   o[3] = 0x03;                                         // LZ flags (lz.hpp:98)
-  const int img = tile_img(j, t);
-  const bool last = j.nimg > 1 ? (t + 1) % j.img_tiles == 0 : t + 1 == j.ntiles;
+  const int img = MTAB ? mt[t].img : tile_img(j, t);
+  const bool last = MTAB ? t + 1 == first[img + 1] : j.nimg > 1 ? (t + 1) % j.img_tiles == 0 : t + 1 == j.ntiles;
   if (j.write_table && !last)                          // choh.cpp:496-498
     hoh_write_varint(j.out + (j.nimg > 1 ? (uint64_t)img * j.out_stride : 0), ti.pad, ti.size);
   if (ti.mode == 127) {                                // indexed layer header (layer_encode.hpp:57, :320-325)
@@ -170,6 +195,12 @@ __global__ __launch_bounds__(64) void k_tilebytes(EncodeJob j) {
       q[0] = 0x10; q[1] = 0; q[2] = 0; q[3] = 0x00; q[4] = 0x10;
     }
   }
+}
+
+__global__ __launch_bounds__(64) void k_tilebytes(EncodeJob j) { tilebytes<false>(j, nullptr, nullptr, nullptr, nullptr); }
+__global__ __launch_bounds__(64) void k_tilebytes_mtab(EncodeJob j, const MixedTile* mt, const int32_t* first,
+                                                       uint64_t* ttotal, uint32_t* terr) {
+  tilebytes<true>(j, mt, first, ttotal, terr);
 }
 
 __global__ __launch_bounds__(256) void k_streambytes(EncodeJob j) {
@@ -243,6 +274,23 @@ void launch_layout(const EncodeJob& j, hipStream_t s) {
 
 void launch_layout_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s) {
   hipLaunchKernelGGL(k_layout_mixed, dim3(j.nimg), dim3(1024), 0, s, j, d);
+}
+
+void launch_layout_mtab(const EncodeJob& j, const MixedDims& d, const MixedTab& tab, hipStream_t s) {
+  hipLaunchKernelGGL(k_layout_mtab, dim3(j.nimg), dim3(1024), 0, s, j, d, (const int32_t*)tab.first);
+}
+
+void launch_assemble_mtab(const EncodeJob& j, const MixedTab& tab, int nstreams, hipStream_t s) {
+  hipLaunchKernelGGL(k_tilebytes_mtab, dim3((j.ntiles + 63) / 64), dim3(64), 0, s, j, (const MixedTile*)tab.tile,
+                     (const int32_t*)tab.first, tab.ttotal, tab.terr);
+  // the streams: k_streambytes as it is, on the job seen tile by tile (its file_ok reads img_total /
+  // img_err at t / img_tiles: the per-tile copies k_tilebytes_mtab just made)
+  EncodeJob jt = j;
+  jt.nimg = j.ntiles > 1 ? j.ntiles : 2;             // > 1: the batch form of file_ok
+  jt.img_tiles = 1;
+  jt.img_total = tab.ttotal;
+  jt.img_err = tab.terr;
+  hipLaunchKernelGGL(k_streambytes, dim3(nstreams), dim3(256), 0, s, jt);
 }
 
 void launch_assemble(const EncodeJob& j, int nstreams, hipStream_t s) {

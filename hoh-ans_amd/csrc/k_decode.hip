@@ -220,6 +220,94 @@ __global__ __launch_bounds__(1024) void k_dtable(DecJob j) {
   if (tid == 0 && tiles[nt - 1].off >= fend) atomicOr(j.gerr, 1u);
 }
 
+// The front of a mixed batch with tiled images (it replaces k_dmixed there): k_dtable's work with a
+// tile count of the file's own.  One workgroup per file f: its tiles are [T_f, T_f+1) of the tile
+// table, which also gives their rectangles on the surface; its prefix is the header its (W, H) imply
+// and, for a tiled image, the tiling bytes -- both checked here against the file -- then the size
+// table (as k_dtable parses it) turned into offsets.  Every read of file f stays inside
+// [f * stride, (f + 1) * stride).  A kernel of its own: k_dtable compiles as it did before.
+__global__ __launch_bounds__(1024) void k_dtable_mtab(DecJob j, MixedDims md, const MixedTile* mt, const int32_t* tfirst) {
+  if (dec_abort(j)) return;
+  __shared__ uint64_t wsum[17];
+  __shared__ uint64_t tend;
+  __shared__ int serial;
+  const int tid = threadIdx.x, f = blockIdx.x;
+  const int ib = tfirst[f], nt = tfirst[f + 1] - ib, nv = nt - 1;
+  const uint64_t fb = j.nimg > 1 ? (uint64_t)f * j.in_stride : 0;
+  const uint64_t fend = j.nimg > 1 ? min((uint64_t)j.size, fb + j.in_stride) : (uint64_t)j.size;
+  uint8_t hb[16];
+  const uint32_t hl = mixed_prefix_bytes(md, f, hb);
+  uint32_t want = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 14; k++)
+    if (k == (uint32_t)tid) want = hb[k];
+  if ((uint32_t)tid < hl && (fb + hl > fend || j.in[fb + tid] != want)) atomicOr(j.gerr, 1u);
+  DecTile* tiles = j.tiles + ib;
+  for (int i = tid; i < nt; i += 1024) {
+    const MixedTile m = mt[ib + i];
+    DecTile t;
+    t.x0 = m.x0; t.y0 = m.y0; t.w = m.w; t.h = m.h;
+    t.off = 0;
+    t.mode = 0; t.nmatch = 0; t.err = 0; t.gen = 0;
+    tiles[i] = t;
+  }
+  const uint64_t p0 = fb + hl;
+  if (tid == 0) { tend = p0; serial = 0; }
+  __syncthreads();
+  if (nv > 0) {
+    const uint64_t end = min(fend, p0 + 3ull * nv);
+    uint64_t cnt = 0;
+    for (uint64_t base = p0; base < end && cnt < (uint64_t)nv; base += 1024) {
+      const uint64_t pos = base + tid;
+      const uint32_t b = pos < end ? j.in[pos] : 0xffu;
+      const bool term = pos < end && b < 0x80;
+      uint64_t tot;
+      const uint64_t incl = block_scan_1024(term ? 1 : 0, wsum, &tot);
+      const uint64_t idx = cnt + incl - 1;
+      if (term && idx < (uint64_t)nv) {
+        const bool b1 = pos >= p0 + 1 && j.in[pos - 1] >= 0x80;
+        const bool b2 = b1 && pos >= p0 + 2 && j.in[pos - 2] >= 0x80;
+        const bool b3 = b2 && pos >= p0 + 3 && j.in[pos - 3] >= 0x80;
+        if (b3) serial = 1;
+        uint64_t v = b;
+        if (b2) v = ((uint64_t)(j.in[pos - 2] & 0x7f) << 14) + ((uint64_t)(j.in[pos - 1] & 0x7f) << 7) + b;
+        else if (b1) v = ((uint64_t)(j.in[pos - 1] & 0x7f) << 7) + b;
+        tiles[idx + 1].off = v;
+        if (idx == (uint64_t)nv - 1) tend = pos + 1;
+      }
+      cnt += tot;
+    }
+    __syncthreads();
+    if (cnt < (uint64_t)nv) serial = 1;
+    __syncthreads();
+    if (serial && tid == 0) {                       // exact varint.hpp:6-27 walk
+      uint64_t p = p0;
+      bool ok = true;
+      for (int i = 0; i < nv; i++) {
+        if (p + 3 > fend) { ok = false; break; }
+        tiles[i + 1].off = rd_varint(j.in, p);
+      }
+      tend = p;
+      if (!ok) atomicOr(j.gerr, 1u);
+    }
+  }
+  __syncthreads();
+  uint64_t carry = tend;
+  for (int i0 = 0; i0 < nt; i0 += 1024) {
+    const int i = i0 + tid;
+    const uint64_t v = i < nt ? tiles[i].off : 0;
+    // no tile is empty (its framing alone is four bytes): a zero in the size table is a table that
+    // was cut short
+    if (i > 0 && i < nt && v == 0) atomicOr(j.gerr, 1u);
+    uint64_t tot;
+    const uint64_t incl = block_scan_1024(v, wsum, &tot);
+    if (i < nt) tiles[i].off = carry + incl;     // tiles[0].off holds 0
+    carry += tot;
+  }
+  __syncthreads();
+  if (tid == 0 && tiles[nt - 1].off >= fend) atomicOr(j.gerr, 1u);
+}
+
 // parse one entropy stream starting at byte p (all lanes, uniform control flow)
 __device__ bool parse_stream(const DecJob& j, uint64_t& p, int sid, uint64_t out_off, int lane) {
   DecStream d;
@@ -352,7 +440,8 @@ __device__ bool parse_stream(const DecJob& j, uint64_t& p, int sid, uint64_t out
 
 // REGION: a region job (k_dparse_gid), whose tile t belongs to the file gid names; the other jobs'
 // k_dparse compiles as it did before the region calls existed
-template <bool REGION>
+// REGION 2 (k_dparse_file, a mixed batch with tiled images): gid[t] is the tile's file itself
+template <int REGION>
 __device__ __forceinline__ void dparse_tile(const DecJob& job) {
   if (dec_abort(job)) return;
   const int t = blockIdx.x, lane = threadIdx.x;
@@ -360,7 +449,8 @@ __device__ __forceinline__ void dparse_tile(const DecJob& job) {
   // (file i is [i * in_stride, (i + 1) * in_stride)), so a truncated file reads as corrupt instead
   // of running on into the next file's bytes
   DecJob j = job;
-  if (j.nimg > 1) j.size = min(job.size, (uint64_t)((REGION ? (int)j.gid[t] / j.file_tiles : t / j.img_tiles) + 1) * j.in_stride);
+  if (j.nimg > 1)
+    j.size = min(job.size, (uint64_t)((REGION == 2 ? (int)j.gid[t] : REGION ? (int)j.gid[t] / j.file_tiles : t / j.img_tiles) + 1) * j.in_stride);
   DecTile ti = j.tiles[t];
   uint64_t p = ti.off;
   bool ok = p + 4 <= j.size;
@@ -448,8 +538,9 @@ __device__ __forceinline__ void dparse_tile(const DecJob& job) {
   }
 }
 
-__global__ __launch_bounds__(64) void k_dparse(DecJob job) { dparse_tile<false>(job); }
-__global__ __launch_bounds__(64) void k_dparse_gid(DecJob job) { dparse_tile<true>(job); }
+__global__ __launch_bounds__(64) void k_dparse(DecJob job) { dparse_tile<0>(job); }
+__global__ __launch_bounds__(64) void k_dparse_gid(DecJob job) { dparse_tile<1>(job); }
+__global__ __launch_bounds__(64) void k_dparse_file(DecJob job) { dparse_tile<2>(job); }
 
 // match the decoder's streams to the side index by payload position
 __global__ void k_dmatch(DecJob j, int nstreams) {
@@ -3351,6 +3442,55 @@ int decode_regions_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t str
 // j.we stands for it -- a width that is no multiple of 16 if the class has one (full2 = 0: the
 // multiple-of-16 chain and k_dexpand are for classes where EVERY width is one), else any of its
 // widths, else tw (no second class).
+// With tiled images in the batch (any side of 512 or more; n >= 2) the files carry different tile
+// counts: ONE job still, over the tiles of all files.  The surface is packed vertically (pitch =
+// the widest IMAGE rounded up to 16 px, image i on rows [Y_i, Y_i + H_i)); j.tw x j.th is the largest
+// TILE of the job (under 512 wide for every shape, so the LDS rows, rings and bands hold), class 1
+// the tiles of that width, class 2 every other width across all the tile grids -- j.we stands for it
+// as above, and full2 holds only if every one of those widths is a multiple of 16.  blk_ok stays
+// tw == 256: in a wider job 256-wide tiles take the flat layout.
+static int decode_mixed_tab(hoh_ctx* c, MixedJob& mj, const uint8_t* d_in, size_t stride, const hoh_index* idx,
+                            uint64_t* d_status, hipStream_t s) {
+  const MixedDims& d = mj.d;
+  const int n = d.n;
+  int tw = 0, th = 0;
+  int64_t rows = 0, ntiles = 0;
+  for (int i = 0; i < n; i++) {
+    int xt, yt, w, h;
+    mixed_tiling(d.wh[2 * i], d.wh[2 * i + 1], xt, yt, w, h);
+    tw = std::max(tw, w);
+    th = std::max(th, h);
+    rows += d.wh[2 * i + 1];
+    ntiles += (int64_t)xt * yt;
+  }
+  if (rows > (1ll << 30) || ntiles > (1 << 24)) return 1;
+  // the second class: every tile width but the widest, the edge columns included
+  int we = tw;
+  for (int i = 0; i < n; i++) {
+    int xt, yt, w, h;
+    mixed_tiling(d.wh[2 * i], d.wh[2 * i + 1], xt, yt, w, h);
+    const int ws[2] = {w, d.wh[2 * i] - (xt - 1) * w};
+    for (int k = 0; k < 2; k++)
+      if (ws[k] != tw && (we == tw || (we % 16 == 0 && ws[k] % 16 != 0))) we = ws[k];
+  }
+  mj.rows = (int)rows;
+  AsyncDec as;
+  as.hdr[0] = as.hdr[1] = 0;
+  as.hl = 0;                                      // k_dtable_mtab checks the headers
+  as.status = d_status;
+  as.bytes = 0;
+  DecJob j;
+  memset(&j, 0, sizeof(j));
+  j.W = d.pitch; j.H = (int)rows;                 // the staging surface (decode_run points j.rgb at it)
+  j.xt = 1; j.yt = (int)ntiles; j.tw = tw; j.th = th;
+  j.we = we;
+  j.ntiles = (int)ntiles;
+  j.nimg = n; j.img_tiles = 1; j.in_stride = stride;
+  j.in = d_in;
+  j.size = (uint64_t)n * stride;
+  return decode_run(c, j, idx, s, &as, nullptr, &mj);
+}
+
 int decode_mixed_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t stride, const int32_t* h_wh, uint8_t* d_rgb,
                             const hoh_index* idx, uint64_t* d_status, hipStream_t s) {
   MixedJob mj;
@@ -3364,6 +3504,10 @@ int decode_mixed_async_impl(hoh_ctx* c, int n, const uint8_t* d_in, size_t strid
   }
   d.pitch = (d.wmax + 15) & ~15;
   mj.dst = d_rgb;
+  mj.tiled = 0;
+  mj.rows = 0;
+  for (int i = 0; i < n; i++) mj.tiled |= (d.wh[2 * i] >= 512 || d.wh[2 * i + 1] >= 512) ? 1 : 0;
+  if (mj.tiled) return decode_mixed_tab(c, mj, d_in, stride, idx, d_status, s);
   int we = d.wmax;
   for (int i = 0; i < n; i++) {
     const int wi = d.wh[2 * i];
@@ -3505,7 +3649,14 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     j.file_tiles = a.file_tiles;
   }
   // a mixed-shape batch: the staging surface of one pitch (a slab of hmax rows per file)
-  if (mx) {
+  MixedTab mtab;
+  memset(&mtab, 0, sizeof(mtab));
+  if (mx && mx->tiled) {
+    if ((e = dbuf(w, 16, (size_t)mx->d.pitch * (size_t)mx->rows * 3 + 16, &q))) return e; j.rgb = (uint8_t*)q;
+    if ((e = dbuf(w, 19, mixed_tab_bytes(nfiles, j.ntiles), &q))) return e;
+    mtab = mixed_tab_at(q, nfiles, j.ntiles, mx->d.pitch, mx->rows);
+    j.gid = mtab.tfile;                            // k_dparse_file: the tile's file
+  } else if (mx) {
     if ((e = dbuf(w, 16, (size_t)mx->d.pitch * mx->d.hmax * nfiles * 3 + 16, &q))) return e; j.rgb = (uint8_t*)q;
   }
   j.lz_xrow = lz_xrow(j.nimg > 1);
@@ -3524,7 +3675,13 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   ctx_mark(c, s, "start", as == nullptr);
   const int nfile = j.nimg > 1 ? j.nimg : 1;
   if (as && as->hl) hipLaunchKernelGGL(k_dhdr, dim3(nfile), dim3(64), 0, s, j, as->hdr[0], as->hdr[1], as->hl);
-  if (mx) {
+  if (mx && mx->tiled) {
+    // the tile table, then per file: header and tiling bytes against its own shape, its size table
+    // turned into offsets, one DecTile per tile
+    launch_mtab(mx->d, mtab, s);
+    hipLaunchKernelGGL(k_dtable_mtab, dim3(nfile), dim3(1024), 0, s, j, mx->d, (const MixedTile*)mtab.tile,
+                       (const int32_t*)mtab.first);
+  } else if (mx) {
     // each file's header against its own shape, and its one tile's DecTile
     launch_dmixed(mx->d, j.in, j.size, nfile > 1 ? j.in_stride : j.size, j.tiles, j.gerr, s);
   } else if (rg) {
@@ -3543,6 +3700,7 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
   }
   ctx_mark(c, s, "dtable", false);
   if (rg) hipLaunchKernelGGL(k_dparse_gid, dim3(j.ntiles), dim3(64), 0, s, j);
+  else if (mx && mx->tiled) hipLaunchKernelGGL(k_dparse_file, dim3(j.ntiles), dim3(64), 0, s, j);
   else hipLaunchKernelGGL(k_dparse, dim3(j.ntiles), dim3(64), 0, s, j);
   ctx_mark(c, s, "dparse", false);
   if (indexed) {
@@ -3644,7 +3802,8 @@ static int decode_run(hoh_ctx* c, DecJob& j, const hoh_index* idx, hipStream_t s
     ctx_mark(c, s, "dcrop", false);
   }
   if (mx) {                                                            // the images, out of the staging surface
-    launch_mscatter(mx->d, j.rgb, mx->dst, j.gerr, s);
+    if (mx->tiled) launch_mscatter_tab(mtab, j.rgb, mx->dst, j.gerr, s);
+    else launch_mscatter(mx->d, j.rgb, mx->dst, j.gerr, s);
     ctx_mark(c, s, "mscatter", false);
   }
   if (hipGetLastError() != hipSuccess) return 3;

@@ -88,9 +88,14 @@ __device__ __forceinline__ uint32_t px_mem(const uint8_t* img, size_t pitch, int
 // MixedDims) its own w x h at the top left of slab t of the staging surface.  The variants are
 // instantiations of their own (k_front_mixed, k_colours_mixed): the kernels of the other entry
 // points compile as they did before.
-template <bool MIXED>
-__device__ __forceinline__ void tile_rect(const EncodeJob& j, const MixedDims* md, int t, int& x0, int& y0, int& w, int& h) {
-  if (MIXED) {
+// MIXED 2 (a mixed batch with tiled images, MixedTab): the rectangle the tile table gives.
+template <int MIXED>
+__device__ __forceinline__ void tile_rect(const EncodeJob& j, const MixedDims* md, int t, int& x0, int& y0, int& w, int& h,
+                                          const MixedTile* mt = nullptr) {
+  if (MIXED == 2) {
+    const MixedTile m = mt[t];
+    x0 = m.x0; y0 = m.y0; w = m.w; h = m.h;
+  } else if (MIXED) {
     x0 = 0; y0 = t * j.th;
     w = md->wh[2 * t]; h = md->wh[2 * t + 1];
   } else {
@@ -100,8 +105,9 @@ __device__ __forceinline__ void tile_rect(const EncodeJob& j, const MixedDims* m
   }
 }
 
-template <bool RINGED, uint32_t RG, bool MIXED = false>
-__device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring, const MixedDims* md = nullptr) {
+template <bool RINGED, uint32_t RG, int MIXED = 0>
+__device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring, const MixedDims* md = nullptr,
+                                           const MixedTile* mt = nullptr) {
   __shared__ uint32_t wkey[4][WTAB + 1];
   __shared__ uint32_t wdup[4][WTAB / 32];
   __shared__ uint32_t hist[3 * 512 - 256];         // G: 256 bins at 0, R': 512 at 256, B': 512 at 768
@@ -109,7 +115,7 @@ __device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring, c
 
   const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   int x0, y0, w, h;
-  tile_rect<MIXED>(j, md, t, x0, y0, w, h);
+  tile_rect<MIXED>(j, md, t, x0, y0, w, h, mt);
   const uint32_t npix = (uint32_t)w * h;
   for (int i = tid; i < 3 * 512 - 256; i += NT) hist[i] = 0;
   for (int i = lane; i <= WTAB; i += 64) wkey[wv][i] = 0;
@@ -314,15 +320,15 @@ __device__ __forceinline__ void front_tile(const EncodeJob& j, uint32_t* ring, c
 // palette in first-occurrence order (choh.cpp:64-88).  One workgroup per tile walks raster blocks
 // and stops as soon as a tile has shown 257 colours, which natural tiles do within a block or
 // two, so k_front carries no colour set (and fits seven workgroups per CU).
-template <bool MIXED>
-__device__ __forceinline__ void colours_tile(const EncodeJob& j, const MixedDims* md) {
+template <int MIXED>
+__device__ __forceinline__ void colours_tile(const EncodeJob& j, const MixedDims* md, const MixedTile* mt = nullptr) {
   __shared__ uint32_t hset[CSET];
   __shared__ uint32_t hpos[CSET];                   // first raster position of each colour
   __shared__ uint32_t pc[256], pp[256];
   __shared__ int s_ncol, s_np;
   const int t = blockIdx.x, tid = threadIdx.x;
   int x0, y0, w, h;
-  tile_rect<MIXED>(j, md, t, x0, y0, w, h);
+  tile_rect<MIXED>(j, md, t, x0, y0, w, h, mt);
   const uint32_t npix = (uint32_t)w * h;
   const uint8_t* img = j.rgb + ((size_t)y0 * j.W + x0) * 3;
   const size_t pitch = (size_t)j.W * 3;
@@ -388,8 +394,9 @@ __device__ __forceinline__ void colours_tile(const EncodeJob& j, const MixedDims
   if (tid == 0) j.ncol[t] = s_ncol;
 }
 
-__global__ __launch_bounds__(NT) void k_colours(EncodeJob j) { colours_tile<false>(j, nullptr); }
-__global__ __launch_bounds__(NT) void k_colours_mixed(EncodeJob j, MixedDims d) { colours_tile<true>(j, &d); }
+__global__ __launch_bounds__(NT) void k_colours(EncodeJob j) { colours_tile<0>(j, nullptr); }
+__global__ __launch_bounds__(NT) void k_colours_mixed(EncodeJob j, MixedDims d) { colours_tile<1>(j, &d); }
+__global__ __launch_bounds__(NT) void k_colours_mtab(EncodeJob j, const MixedTile* mt) { colours_tile<2>(j, nullptr, mt); }
 
 template <uint32_t RG>
 __global__ __launch_bounds__(NT) void k_front(EncodeJob j) {
@@ -400,7 +407,13 @@ __global__ __launch_bounds__(NT) void k_front(EncodeJob j) {
 template <uint32_t RG>
 __global__ __launch_bounds__(NT) void k_front_mixed(EncodeJob j, MixedDims d) {
   __shared__ uint32_t ring[2 * RG + 4];
-  front_tile<true, RG, true>(j, ring, &d);
+  front_tile<true, RG, 1>(j, ring, &d);
+}
+
+template <uint32_t RG>
+__global__ __launch_bounds__(NT) void k_front_mtab(EncodeJob j, const MixedTile* mt) {
+  __shared__ uint32_t ring[2 * RG + 4];
+  front_tile<true, RG, 2>(j, ring, nullptr, mt);
 }
 
 __global__ __launch_bounds__(NT) void k_front_wide(EncodeJob j) { front_tile<false, 1>(j, nullptr); }
@@ -938,4 +951,12 @@ void launch_front_mixed(const EncodeJob& j, const MixedDims& d, hipStream_t s) {
   hipLaunchKernelGGL(k_colours_mixed, dim3(j.ntiles), dim3(NT), 0, s, j, d);
   if (j.tw <= RING_SMALL_MAX_W) hipLaunchKernelGGL(k_front_mixed<RING_SMALL>, dim3(j.ntiles), dim3(NT), 0, s, j, d);
   else hipLaunchKernelGGL(k_front_mixed<RING>, dim3(j.ntiles), dim3(NT), 0, s, j, d);
+}
+
+// A mixed batch with tiled images: every tile's rectangle from the tile table (tiles under 512 wide
+// for every tiled shape and the small class alike; j.tw is the widest).  Never k_front256 either.
+void launch_front_mtab(const EncodeJob& j, const MixedTab& tab, hipStream_t s) {
+  hipLaunchKernelGGL(k_colours_mtab, dim3(j.ntiles), dim3(NT), 0, s, j, (const MixedTile*)tab.tile);
+  if (j.tw <= RING_SMALL_MAX_W) hipLaunchKernelGGL(k_front_mtab<RING_SMALL>, dim3(j.ntiles), dim3(NT), 0, s, j, (const MixedTile*)tab.tile);
+  else hipLaunchKernelGGL(k_front_mtab<RING>, dim3(j.ntiles), dim3(NT), 0, s, j, (const MixedTile*)tab.tile);
 }

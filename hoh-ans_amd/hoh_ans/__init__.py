@@ -90,6 +90,8 @@ def lib():
             ("hoh_index_deserialize", [vp, C.c_char_p, sz, vp]),
             ("hoh_index_build", [vp, vp, sz, vp, ip, ip, vp]),
             ("hoh_index_concat", [vp, C.c_int, C.POINTER(vp), C.c_uint64, vp]),
+            ("hoh_index_join", [vp, C.c_int, C.POINTER(vp), C.c_uint64, vp]),
+            ("hoh_index_file", [vp, C.c_int, vp, vp]),
             ("hoh_decode_image", [vp, vp, sz, vp, sz, ip, ip, vp]),
             ("hoh_decode_image_ix", [vp, vp, sz, vp, sz, ip, ip, vp, vp]),
             ("hoh_encode_image_async", [vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
@@ -307,6 +309,23 @@ class Index:
         check(lib().hoh_index_concat(ix.h, len(indexes), hs, stride, None), "hoh_index_concat")
         return ix
 
+    @classmethod
+    def join(cls, indexes, stride):
+        """hoh_index_join: concat for files of different tile counts (a mixed batch with tiled
+        images); to_bytes() of the result raises E_UNSUPPORTED where the counts differ."""
+        ix = cls()
+        hs = (vp * len(indexes))(*[i.h for i in indexes])
+        check(lib().hoh_index_join(ix.h, len(indexes), hs, stride, None), "hoh_index_join")
+        return ix
+
+    def file(self, i, ctx=None):
+        """hoh_index_file: file i's own index out of this batch index (payload offsets rebased to the
+        file's start); serializes to the blob of the image encoded alone.  ctx as in to_bytes."""
+        ix = Index()
+        s = vp(lib().hoh_ctx_stream(ctx.h)) if ctx is not None else None
+        check(lib().hoh_index_file(self.h, int(i), ix.h, s), "hoh_index_file")
+        return ix
+
     def __del__(self):
         try:
             if self.h:
@@ -434,7 +453,7 @@ def mixed_rgb_bytes(shapes):
 
 
 def encode_mixed_async(rgb_dev, shapes, out_dev, stride, status_dev, ctx=None, index=None, speed=0):
-    """Enqueue-only hoh_encode_mixed_async: len(shapes) small-class images of shapes[i] = (W, H),
+    """Enqueue-only hoh_encode_mixed_async: len(shapes) images (tiled or small class) of shapes[i] = (W, H),
     packed back to back in rgb_dev (mixed_rgb_bytes), into files at out_dev + i*stride; status_dev:
     int64 tensor of 2n ({code, size} per image).  At -s0 the batch is one job and `index` records its
     side index; the context needs no option."""
@@ -753,9 +772,9 @@ def choh(rgb, ctx=None, speed=0, decodable=None, small=None):
 
 
 def choh_mixed(images, ctx=None, speed=0, decodable=None):
-    """A list of (H, W, 3) uint8 arrays of the small class, any mix of shapes -> the list of their
-    .hoh files (header || tile, as choh(..., small=True) writes each), coded by one
-    hoh_encode_mixed_async call.  decodable as in choh."""
+    """A list of (H, W, 3) uint8 arrays, tiled shapes and the small class in any mix -> the list of
+    their .hoh files (a tiled image's as choh writes it, a small one's header || tile as
+    choh(..., small=True) does), coded by one hoh_encode_mixed_async call.  decodable as in choh."""
     import torch
     ctx = ctx or default_ctx()
     imgs = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
@@ -784,7 +803,7 @@ def choh_mixed(images, ctx=None, speed=0, decodable=None):
 
 
 def dhoh_mixed(files, shapes, ctx=None):
-    """The inverse of choh_mixed: a list of small-class .hoh files and their (W, H) -> the list of
+    """The inverse of choh_mixed: a list of tiled or small-class .hoh files and their (W, H) -> the list of
     (H, W, 3) arrays, decoded by one hoh_decode_mixed_async call."""
     import torch
     ctx = ctx or default_ctx()

@@ -218,6 +218,20 @@ int hoh_index_build(hoh_ctx* ctx, const uint8_t* d_hoh, size_t size, hoh_index* 
  * Serializes to the bytes of the index hoh_encode_images_async(n, .., stride, idx) records for the
  * same files.  n == 1 copies (stride ignored). */
 int hoh_index_concat(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream);
+/* A batch whose files carry DIFFERENT tile counts (hoh_encode_mixed_async with tiled images among
+ * its shapes) has an index the version-1 blob cannot hold (one stream count for all files):
+ * hoh_index_serialize answers HOH_E_UNSUPPORTED for it and hoh_index_serialized_size 0.  Such an
+ * index is persisted file by file:
+ * hoh_index_file: dst = file i's own index out of a batch's (recorded, concatenated or joined):
+ * payload offsets rebased by i * stride, nimg = 1.  It serializes to the bytes of the index
+ * hoh_encode_image_ix records for image i alone.  HOH_E_ARG for i outside the batch; an empty batch
+ * index gives an empty dst for any i >= 0.  dst must not be batch.
+ * hoh_index_join: hoh_index_concat for any stream counts that are multiples of 7 (HOH_E_ARG
+ * otherwise, and for an empty source beside non-empty ones).  Where the counts are equal dst
+ * serializes to hoh_index_concat's bytes.  A decode with dst needs the same n and stride (else
+ * HOH_E_ARG), as with any batch index. */
+int hoh_index_file(const hoh_index* batch, int i, hoh_index* dst, void* stream);
+int hoh_index_join(hoh_index* dst, int n, const hoh_index* const* src, uint64_t stride, void* stream);
 
 /* Replaces dhoh.cpp:297-396 (with the decoder defects of SURVEY Q1, Q9-Q12 fixed).  d_hoh holds
  * `size` bytes of a .hoh file; writes W*H*3 RGB bytes to d_rgb.  Every decode entry point reads,
@@ -280,39 +294,53 @@ int hoh_encode_images_async(hoh_ctx* ctx, int n, const uint8_t* d_rgb, int W, in
 int hoh_decode_images_async(hoh_ctx* ctx, int n, const uint8_t* d_hoh, size_t stride, int W, int H, uint8_t* d_rgb,
                             const hoh_index* idx, uint64_t* d_status, void* stream);
 
-/* ---- mixed-shape batches of small images ---------------------------------------------------
- * n images of the small class (W <= 511 and H <= 511, see HOH_OPT_SMALL_IMAGES), each with its own
- * shape, per call: a folder of thumbnails, crops or dataset samples without one call per image and
- * without padding.  h_wh (host) holds W_0, H_0, W_1, H_1, ... and is read only during the call.  The
- * images are packed back to back on both sides: image i is W_i*H_i*3 bytes at d_rgb + offsets[i]
- * (hoh_mixed_rgb_bytes).  File i is written at / read from d_hoh + i*stride as in
+/* ---- mixed-shape batches: tiled images and small ones in one job ------------------------------
+ * n images, each with its own shape, per call: a folder of photos, thumbnails, crops or dataset
+ * samples without one call per image and without padding.  Shapes: every shape hoh_tiling tiles
+ * ((W >= 512 || H >= 512) && W >= 256 && H >= 256), the small class (W <= 511 and H <= 511, see
+ * HOH_OPT_SMALL_IMAGES), and any mix of both in any order; the remaining untiled shapes (one side
+ * under 256, the other 512 or more, e.g. 512 x 10) are HOH_E_UNSUPPORTED.  h_wh (host) holds W_0,
+ * H_0, W_1, H_1, ... and is read only during the call.  The images are packed back to back on both
+ * sides: image i is W_i*H_i*3 bytes at d_rgb + offsets[i] (hoh_mixed_rgb_bytes; 64-bit: tiled
+ * images pass 2^32 bytes together).  File i is written at / read from d_hoh + i*stride as in
  * hoh_*_images_async; d_status holds 2n u64, {status, size} per image (decode: size = W_i*H_i*3).
- * Both calls are enqueue-only and need no context option: they are new, and always write and read
- * the small-class single-tile file, header || tile.  HOH_OPT_DECODABLE, HOH_OPT_NOIX_DECODER and
- * HOH_OPT_CHAIN_TABLES apply as everywhere else.  File i is byte-identical to what hoh_encode_image
- * writes for image i under HOH_OPT_SMALL_IMAGES at the same speed and options.
- * Encode: at -s0 the whole batch is ONE job (the n images are the n tiles of a stack of Wmax x Hmax
- * slabs on a staging surface in the context's workspace), and idx, if given, records the batch's
- * side index: nimg = n, the batch's stride, serialising to the bytes of hoh_index_concat over the n
- * single-image indexes.  At -s1..-s4 maximal runs of consecutive equal shapes run as uniform small
- * stacks one after another (a run of one as a single image), and idx is emptied as in the other
- * -s>=1 calls; between two runs the host waits for the stream, because the search's log2 tables are
- * per pixel count and the host rebuilds them (as in any sequence of -s>=1 calls of changing shape).  An image's own failure (HOH_E_CAP past its stride, HOH_E_UNREPRODUCIBLE) marks only
- * its slot.
- * Decode: one job for every file kind the small-class decoder reads (decodable -s>=1 general tiles
- * and RGB mode included), with the index, without it, and under every HOH_OPT_NOIX_DECODER choice.
- * The caller gives every W and H; each file's header is checked on the device (a mismatch:
+ * Both calls are enqueue-only and need no context option.  File i is what the synchronous call
+ * writes for image i alone, byte for byte, at the same speed and options: a tiled image gives
+ * hoh_encode_image's file (header, the two tiling bytes, the tile size table, the tiles), a small
+ * image header || tile (hoh_encode_image under HOH_OPT_SMALL_IMAGES).  HOH_OPT_DECODABLE,
+ * HOH_OPT_NOIX_DECODER and HOH_OPT_CHAIN_TABLES apply as everywhere else.
+ * Encode: at -s0 the whole batch is ONE job over the tiles of all its files.  The images pass through
+ * a staging surface in the context's workspace: all of the small class, a stack of Wmax x Hmax slabs;
+ * with tiled images among them, one surface of pitch Wmax packed vertically, image i on rows
+ * [Y_i, Y_i + H_i), Y_i the sum of the heights before it, and a tile table built on the device (one
+ * very wide image beside many narrow ones still wastes surface).  idx, if given, records the batch's
+ * side index: nimg = n, the batch's stride.  Where all files have the same tile count it serialises
+ * to the bytes of hoh_index_concat over the n single-image indexes (for a uniform tiled batch: the
+ * blob hoh_encode_images_async records); where they differ, see hoh_index_file / hoh_index_join.
+ * At -s1..-s4 maximal runs of consecutive equal shapes run as uniform batches one after another (a
+ * run of a tiled shape as hoh_encode_images_async does it, a run of one as a single image), and idx
+ * is emptied as in the other -s>=1 calls; between two runs the host waits for the stream, because
+ * the search's log2 tables are per pixel count (at most four per job; one tiled shape uses up to
+ * four by itself) and the host rebuilds them.  An image's own failure (HOH_E_CAP past its stride,
+ * with the size it would need in the size word; HOH_E_UNREPRODUCIBLE) marks only its slot.
+ * Decode: one job for every file kind the full decoder reads (decodable -s>=1 general tiles and RGB
+ * mode included), with the index, without it, and under every HOH_OPT_NOIX_DECODER choice.  The
+ * caller gives every W and H; each file's header and each tiled file's tiling bytes are checked on
+ * the device against (W_i, H_i) (a mismatch, or a size table that runs past the file's stride slot:
  * HOH_E_CORRUPT) and every parse of file i stays inside [i*stride, (i+1)*stride).  An error in any
  * file marks every slot and leaves the caller's d_rgb untouched.
  * Returned at once: HOH_E_ARG for n outside 1..HOH_MIXED_MAX_BATCH, null pointers, a non-positive
- * dimension, or a non-empty index recorded for another n or stride; HOH_E_UNSUPPORTED for a shape
- * outside the small class; HOH_E_CAP (encode) for a stride under 10 bytes, the longest header.
- * Workspaces are grow-only: a repeat call with the same n, Wmax and Hmax allocates nothing, in
- * whatever order the shapes come.
- * Not covered: mixed -s>=1 batches as one job, tiled shapes, hoh_mgpu_*. */
+ * dimension, a sum of heights above 2^30 or more than 2^24 tiles, or a non-empty index recorded for
+ * another n or stride; HOH_E_UNSUPPORTED for a shape neither tiled nor of the small class, and for
+ * a -s0 job past the encoder's 32-bit table bound (~74,000 tiles); HOH_E_CAP (encode) for a stride
+ * under 10 bytes, the longest header of the small class.
+ * Workspaces are grow-only: a repeat call with the same shapes allocates nothing, in whatever
+ * order they come.
+ * Not covered: mixed -s>=1 batches as one job, direct reads and writes of the packed rows (the
+ * images pass through the staging surface), hoh_mgpu_*. */
 #define HOH_MIXED_MAX_BATCH 256
 /* host only: offsets[i] = sum over k < i of 3*W_k*H_k (n+1 entries, may be NULL); returns offsets[n];
- * 0 (offsets untouched) if any shape is outside the small class or n is out of range */
+ * 0 (offsets untouched) if any shape is neither tiled nor of the small class or n is out of range */
 size_t hoh_mixed_rgb_bytes(int n, const int32_t* h_wh, uint64_t* offsets);
 int hoh_encode_mixed_async(hoh_ctx* ctx, int n, const uint8_t* d_rgb, const int32_t* h_wh, int speed,
                            uint8_t* d_out, size_t stride, hoh_index* idx, uint64_t* d_status, void* stream);
